@@ -8,11 +8,16 @@
 One "step" = one pass of the reference's inner loop (`src/eoe/training/ad_trainer.py:428-436`) over one synthetic
 step batch of 128 normal + 128 OE already-normalised images per GPU: zero_grad -> encoder forward -> HSC loss ->
 backward -> (gradient all-reduce) -> Adam -> anomaly scores from the pre-step features.  Inputs are resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line (contract in the task description), with two extra objects:
+before the timed region.  Rank 0 prints ONE JSON line (contract in the task description).  A plain run sets up, warms
+up, times --steps steps and prints the line; everything else it can measure runs only under --full, which adds:
+  box          -- three calibration probes of the GPU, run before the warm-up;
   roofline     -- the dominant kernel family's achieved TFLOP/s (algorithmic flops / hipEvent-measured launch time,
                   collected in a separate profiled pass inside this run) against the dense 16-bit MFMA peak;
   cpu_baseline -- the CPU oracle (a port of the reference step: oracle/) timed on this host's cores on a bounded
-                  sample (N=1, rank 0 only).
+                  sample (N=1, rank 0 only);
+  torch_rocm_baseline -- the same step in stock PyTorch-ROCm ops (N=1, rank 0 only).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32), so that two builds can be
+compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -78,6 +83,12 @@ def parse():
     ap.add_argument("--conv-y16", action="store_true",
                     help="conv nets, fp16: keep the convolution outputs in fp16 in front of BatchNorm (ops.CONV_Y16; a speed option with one "
                          "more rounding point, see DESIGN.md section 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the box probes, the per-kernel roofline pass and the CPU / "
+                         "stock PyTorch baselines (each can still be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy in float32: loss, scores, "
+                         "features and, when training, seeded samples of the updated parameters and of their gradients")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--serial-kernels", action="store_true",
@@ -87,7 +98,7 @@ def parse():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --batch normal (+ as many OE) images per GPU; strong: that many per JOB, split over the ranks")
     ap.add_argument("--no-torch-baseline", action="store_true")
-    ap.add_argument("--no-box-probe", action="store_true", help="skip the three calibration probes in front of the timed region")
+    ap.add_argument("--no-box-probe", action="store_true", help="--full: skip the three calibration probes in front of the timed region")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-steps", type=int, default=5)
     return ap.parse_args()
@@ -244,6 +255,23 @@ def pmc_traffic(kernel):
     return round(per), os.path.relpath(paths[-1], os.path.dirname(os.path.abspath(__file__)))
 
 
+DUMP_MAX_ELEMS = 1 << 20     # an output larger than this is written as a fixed seeded sample of this many elements (4 MB per file)
+
+
+def dump_outputs(out_dir, arrays):
+    """writes each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32; a tensor of more than DUMP_MAX_ELEMS elements is
+    flattened and sampled at the same seeded positions on every run (sorted), so that two builds can be compared element for element"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     import torch
@@ -321,10 +349,12 @@ def main():
     score_buf = torch.empty((args.steps + args.warmup + 8, n_local), dtype=torch.float32, device=dev)
 
     wait_events = []                 # (before, after) events around the wait for the step's collectives: the EXPOSED communication
+    last_feats = [None]              # the latest eager step's features (--dump-outputs); the graph replay keeps its own
 
     def step(i):
         opt.zero_grad()
         feats = model(imgs)
+        last_feats[0] = feats.detach()
         loss = eoe_amd.hsc_loss(feats, lbls, 0, 1.0 / n_global)
         loss.backward()
         if world > 1:
@@ -345,6 +375,7 @@ def main():
         def step(i):                                       # noqa: F811  (eval_cls: forward-only scoring, ad_trainer.py:498-512)
             with torch.no_grad():
                 feats = model(imgs)
+            last_feats[0] = feats
             score_buf[i % score_buf.shape[0]] = eoe_amd.hsc_score(feats)
             return score_buf[i % score_buf.shape[0]][0]
 
@@ -368,7 +399,7 @@ def main():
             return loss
 
     # (every rank runs the probes -- rank 0's numbers go into the line --: the ranks reach the first collective of the warm-up together)
-    box = box_probe(dev) if not args.no_box_probe else None
+    box = box_probe(dev) if args.full and not args.no_box_probe else None
     for i in range(args.warmup):
         loss = step(i)
     sync()
@@ -403,11 +434,23 @@ def main():
     from eoe_amd import metrics
     last = score_buf[(args.warmup + args.steps - 1) % score_buf.shape[0]].float().cpu().numpy()
     auc = float(metrics.roc_auc(lbls.cpu().numpy(), last))
+    if args.dump_outputs and rank == 0:
+        # before the roofline pass, which runs more steps: what a caller of the last timed step receives (the loss, the pre-step anomaly
+        # scores, the features they come from; when training, the updated parameters and their gradients, unscaled)
+        outs = {"scores": score_buf[(args.warmup + args.steps - 1) % score_buf.shape[0]]}
+        if last_feats[0] is not None:
+            outs["features"] = last_feats[0]
+        if training:
+            outs["loss"] = loss
+            ps = [p for p in model.parameters() if p.requires_grad]
+            outs["params"] = torch.cat([p.detach().reshape(-1).float() for p in ps])
+            outs["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in ps]) / eoe_amd.grad_scale()
+        dump_outputs(args.dump_outputs, outs)
 
     roof = None
     if use_graph:
         step = eager_step                                  # the per-kernel profile runs the eager launches
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # separate profiled pass: hipEvents around every kernel launch (inside the library, on the launch stream).  The weight-gradient
         # launches are SERIALISED for this pass: in the timed region they run on a side stream under the next block's / layer's kernels
         # (ops.VIT_ASYNC_WGRAD, ops.CONV_ASYNC_WGRAD), which stretches the durations of whatever shares the chip with them -- a kernel's
@@ -519,9 +562,9 @@ def main():
                            "sync_bn": bool(parallel._bn_sync_cb is not None)}
         if roof is not None:
             out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline and args.model == "vit":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "vit":
             out["cpu_baseline"] = cpu_baseline(args)
-        if world == 1 and not args.no_torch_baseline and args.model == "vit" and training:
+        if args.full and world == 1 and not args.no_torch_baseline and args.model == "vit" and training:
             del model, opt, arena
             torch.cuda.empty_cache()
             out["torch_rocm_baseline"] = torch_rocm_baseline(args, dev)

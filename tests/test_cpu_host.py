@@ -246,3 +246,22 @@ def test_round5_entry_points_validate_their_arguments_without_a_gpu():
     # the gemm argument block's new tail (ABI v5): the stream-K / split-k workspace
     g = _lib.GemmArgs()
     assert hasattr(g, "sk_workspace") and hasattr(g, "sk_workspace_bytes") and _lib.ABI_VERSION == 5
+
+
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: every output as a float32 .npy of its own shape; one of more than DUMP_MAX_ELEMS elements as the same
+    seeded sample (sorted positions) on every call, so that two runs compare element for element"""
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float64)
+    small = torch.arange(12, dtype=torch.float16).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "loss": torch.tensor(0.5)})
+    a_big, b_big = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a_big.dtype == np.float32 and a_big.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a_big, b_big)
+    assert np.all(np.diff(a_big) > 0)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 0.5

@@ -372,8 +372,23 @@ def test_bench_itself_with_two_ranks():
 
 def test_bench_eval_mode_line():
     """`bench.py --mode eval`: the forward-only scoring loop of eval_cls (ad_trainer.py:473-550) as a throughput line"""
-    out = _run_bench(["--mode", "eval", "--steps", "3", "--warmup", "1", "--layers", "2", "--batch", "8", "--no-cpu-baseline"])
+    out = _run_bench(["--mode", "eval", "--steps", "3", "--warmup", "1", "--layers", "2", "--batch", "8", "--no-cpu-baseline", "--full"])
     assert out["metric"].startswith("eval images/sec") and out["value"] > 0 and out["final_loss"] is None
     assert "eval_cls" in out["config"]["workload"]
     r = out["roofline"]
     assert r["kernel"].startswith("gemm") and set(k for k in r["kernels_ms_per_step"] if k.startswith("gemm")) == {"gemm_nt"}   # no wgrad
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """a plain `bench.py` run times its steps and prints the line without the --full measurements (box probes, roofline pass, baselines);
+    --dump-outputs writes what the last timed step computed, in float32, at the shapes of the step"""
+    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--layers", "1", "--batch", "4", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"box", "roofline", "cpu_baseline", "torch_rocm_baseline"} & set(out)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"loss", "scores", "features", "params", "grads"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["loss"].shape == () and abs(float(got["loss"]) - out["final_loss"]) < 1e-5
+    assert got["scores"].shape == (8,) and got["features"].shape[0] == 8
+    assert got["params"].shape == got["grads"].shape and 0 < got["params"].size <= (1 << 20) and np.abs(got["grads"]).max() > 0
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

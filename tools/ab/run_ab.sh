@@ -1,6 +1,7 @@
 # A/B of two builds of the library on ONE box, interleaved: the in-tree build (new) against one built with the files under tools/ab/prev/
 # swapped in (same relative paths; produce them with `git show <rev>:<path> > tools/ab/prev/<path>` -- the GPU box has no git history).
-# Usage: bash tools/ab/run_ab.sh [bench.py arguments]; EOE_PROF_SHAPES=1 for per-shape NT GEMM times.
+# Usage: bash tools/ab/run_ab.sh [bench.py arguments]; --full among them for the per-kernel table, with EOE_PROF_SHAPES=1 for per-shape
+# NT GEMM times.
 set -e
 cd $GRAFT_REPO_ROOT
 ARGS="${@:---steps 20 --warmup 5 --no-cpu-baseline --no-torch-baseline --no-roofline}"

@@ -1,6 +1,7 @@
 # the library built with and without extra compiler flags, interleaved bench runs on one box: bash tools/cflags_ab.sh "-mllvm -amdgpu-kernarg-preload-count=16"
 F="$1"
 ROOF=${ROOF---no-roofline}     # ROOF="" keeps the per-kernel pass: the summary then lists kernels_ms_per_step too
+[ -n "$ROOF" ] || ROOF=--full  # (the per-kernel pass is one of bench.py's --full measurements)
 R=$GRAFT_REPO_ROOT; cd $R
 mkdir -p gpurun_out/cf /tmp/cf
 cp eoe_amd/libeoe_hip.so /tmp/cf/base.so; cp eoe_amd/libeoe_hip.so.stamp /tmp/cf/base.stamp

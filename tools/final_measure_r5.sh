@@ -22,7 +22,7 @@ python tools/pmc_summary.py hbm $ff $fw > $O/bench_pmc_hbm_bytes.csv && cp $O/be
 python tools/pmc_summary.py sq $fs > $O/bench_pmc_sq.csv
 python tools/pmc_summary.py sq $ft > $O/bench_pmc_tcp.csv
 rm -rf $O/pmc_fetch $O/pmc_write $O/pmc_sq $O/pmc_tcp
-b() { name=$1; shift; timeout -k 10 300 python bench.py "$@" > $O/$name.json 2> $O/$name.err; say "$name $(cut -c1-150 $O/$name.json)"; }
+b() { name=$1; shift; timeout -k 10 300 python bench.py --full "$@" > $O/$name.json 2> $O/$name.err; say "$name $(cut -c1-150 $O/$name.json)"; }
 b bench --steps 20 --warmup 5
 b bench_serial --steps 20 --warmup 5 --serial-kernels --no-cpu-baseline --no-torch-baseline
 b bench_frozen --mode frozen --no-cpu-baseline --no-torch-baseline
@@ -38,7 +38,7 @@ p stats_default --kernel-trace --stats -d $R/$O/stats_default -o run -- python $
 p stats --kernel-trace --stats -d $R/$O/stats -o run -- python $R/bench.py --steps 8 --warmup 5 --no-cpu-baseline --no-torch-baseline --no-roofline --no-box-probe --serial-kernels
 for d in stats_default stats; do f=$(db $d); [ -n "$f" ] && python tools/pmc_summary.py stats $f > $O/${d}_kernel_stats.csv; done
 rm -rf $O/stats_default $O/stats
-EOE_PROF_SHAPES=1 timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-torch-baseline --no-box-probe 2>/dev/null > $O/shapes.json
+EOE_PROF_SHAPES=1 timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-torch-baseline --no-box-probe 2>/dev/null > $O/shapes.json
 python - <<'PY' > gpurun_out/r5m/nt_shapes.txt
 import json
 d = json.loads(open("gpurun_out/r5m/shapes.json").read())

@@ -1,15 +1,16 @@
 # per-shape in-step times of the NT GEMMs (serialised roofline pass of bench.py, EOE_PROF_SHAPES=1) for the final build: default kernel choice,
 # with the 160x256x32 two-workgroup kernel off (nt_flags 4096), and with every shape on the one-wave kernel (nt_flags 512); interleaved twice
-mkdir -p gpurun_out/sh
+O=${O:-/tmp/nt_shapes}; mkdir -p $O     # the bench lines (O= elsewhere keeps them)
 for r in 1 2; do for f in 0 4096 512; do
-EOE_PROF_SHAPES=1 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-torch-baseline --nt-flags $f 2>/dev/null > gpurun_out/sh/e_${f}_$r.json
+EOE_PROF_SHAPES=1 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-torch-baseline --nt-flags $f 2>/dev/null > $O/e_${f}_$r.json
 done; done
-python - <<'PY'
-import json
+python - $O <<'PY'
+import json, sys
+O = sys.argv[1]
 res = {}
 for f in (0, 4096, 512):
     for r in (1, 2):
-        d = json.loads(open(f"gpurun_out/sh/e_{f}_{r}.json").read())
+        d = json.loads(open(f"{O}/e_{f}_{r}.json").read())
         k = d["roofline"]["kernels_ms_per_step"]
         for n, v in k.items():
             if n.startswith("nt_"):
