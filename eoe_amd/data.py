@@ -247,6 +247,15 @@ class ResidentImageSource:
         self._g = torch.Generator().manual_seed(seed)
         self._step = 0
 
+    def defer_normalize(self, on: bool = True):
+        """leave Normalize out of the batches and report (mean, std) as `.normalize` for the encoder's fused normalise: the
+        multi-scale modes filter in the [0, 1] pixel scale, before Normalize (training/ad_trainer.py:413-425)"""
+        self._defer = bool(on)
+        self.normalize = (self.mean, self.std) if on and self.mean is not None else None
+
+    def _norm_args(self):
+        return (None, None) if getattr(self, "_defer", False) else (self.mean, self.std)
+
     def _params(self, idx, Hs, Ws):
         n = len(idx)
         top = torch.randint(-self.padding, Hs + self.padding - self.crop + 1, (n,), generator=self._g)
@@ -281,8 +290,9 @@ class ResidentImageSource:
                 src_n, src_o = color_jitter_u8(self.normal, ni, fn, on), color_jitter_u8(self.oe, oi, fo, oo)
                 pn[:, 0] = torch.arange(len(ni), dtype=torch.int32, device=dev)
                 po[:, 0] = torch.arange(len(oi), dtype=torch.int32, device=dev)
-            xn = augment_batch(src_n, pn, (self.crop, self.crop), self.mean, self.std, self.flip_first, self.noise_std, 2 * seed)
-            xo = augment_batch(src_o, po, (self.crop, self.crop), self.mean, self.std, self.flip_first, self.noise_std, 2 * seed + 1)
+            mean, std = self._norm_args()
+            xn = augment_batch(src_n, pn, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, 2 * seed)
+            xo = augment_batch(src_o, po, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, 2 * seed + 1)
             lbls = torch.cat([torch.full((len(ni),), self.nominal_label, dtype=torch.int64),
                               torch.full((len(oi),), self.anomalous_label, dtype=torch.int64)])
             yield torch.cat([xn, xo]), lbls, torch.cat([ni, oi + n_full])      # OE indices offset by the FULL normal set (bases.py:596)
@@ -305,7 +315,7 @@ class ResidentImageSource:
             idx = torch.arange(s, min(s + batch_size, len(self.test_y)))
             p = torch.stack([idx, torch.full_like(idx, (Hs - self.crop) // 2), torch.full_like(idx, (Ws - self.crop) // 2),
                              torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
-            test.append((augment_batch(self.test, p, (self.crop, self.crop), self.mean, self.std, True, 0.0, 0), self.test_y[idx], idx))
+            test.append((augment_batch(self.test, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx))
         return _Train(), test
 
 

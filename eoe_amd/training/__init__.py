@@ -7,6 +7,7 @@ from .dsvdd import DSVDDTrainer
 from .dsad import DSADTrainer
 from .focal import FocalTrainer
 from .clip import ADClipTrainer
+from .multiscale import multiscale_experiment      # noqa: F401
 
 TRAINER = {"hsc": HSCTrainer, "bce": BCETrainer, "dsvdd": DSVDDTrainer, "dsad": DSADTrainer, "focal": FocalTrainer,
            "clip": ADClipTrainer}

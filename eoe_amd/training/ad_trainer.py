@@ -11,8 +11,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
   * the per-half masked Normalize (:413-425) is one affine with the normal class's statistics, fused into the
     encoder's first kernel when the encoder supports it (SURVEY.md section 8a note 1);
   * optional data parallelism (one process per GPU): each rank trains on its rows of every step batch,
-    loss = sum(local) / global batch, gradients summed over RCCL, scores/labels all-gathered for the AUC.
-Datasets, loggers with tensorboard/PDF output, MSMs and the CLIP text objective are out of scope.
+    loss = sum(local) / global batch, gradients summed over RCCL, scores/labels all-gathered for the AUC;
+  * multi-scale modes (`msms`, eoe_amd.msm): lpf / hpf / blur run as HIP kernels on the device batch after `.to(device)`
+    and before the encoder's fused Normalize (:413-425 train, :501-505 test); `sharpen` (Pillow on host images) is not built.
+Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
 import os
@@ -25,6 +27,7 @@ import torch
 
 from .. import ops, parallel
 from ..metrics import ROC, PRC, roc_auc, average_precision, auc_ap_device
+from ..msm import apply_msms, check_supported
 from ..optim import FusedAdam
 
 
@@ -115,8 +118,8 @@ class ADTrainer(ABC):
         # "auto" = on for a BatchNorm encoder trained with lr >= 1e-3 (every BatchNorm runner of the reference: train_cifar.py:17,
         # train_imagenet.py:16), True / False = forced.  The ViT has no BatchNorm and meets the bar in its 16-bit mode.
         self.exact_bn = exact_bn
-        if msms:
-            raise NotImplementedError("multi-scale modes (MSM) are out of scope")
+        self.msms = list(msms or ())
+        check_supported(self.msms)          # sharpen raises NotImplementedError
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -226,6 +229,12 @@ class ADTrainer(ABC):
         return models, {"mean_auc": mean_auc, "mean_avg_prec": mean_avg_prec, "std_auc": std_auc, "cls_aucs": cls_aucs}
 
     # ------------------------------------------------------------------------------------------- hot loop
+    def _msm_source(self, ds):
+        """MSMs filter in the [0, 1] pixel scale, before Normalize: a source that fuses Normalize into its batches
+        (ResidentImageSource) hands (mean, std) to the encoder's fused normalise instead"""
+        if self.msms and hasattr(ds, "defer_normalize"):
+            ds.defer_normalize(True)
+
     def _normalize_hook(self, model, ds):
         """install the (mean, std) of the normal class on an encoder that fuses it; returns a fallback callable for
         encoders that do not"""
@@ -279,6 +288,7 @@ class ADTrainer(ABC):
         cls_roc = None
         opt = self.make_optimizer(model)                                                              # :380-383
         sched = torch.optim.lr_scheduler.MultiStepLR(opt, self.milestones, 0.1)                       # :384
+        self._msm_source(ds)
         loader, _ = ds.loaders(self.batch_size, num_workers=self.workers, persistent=True)              # :385
         ep = self.load(load if isinstance(load, str) else None, model, opt, sched)                      # :396
         center = self.center = self.prepare_metric(clsstr, loader, model, seed)                         # :397
@@ -332,6 +342,8 @@ class ADTrainer(ABC):
                             inv_count, keep_scores = 1.0 / (n_glob * world), rank == 0
                     imgs = imgs.to(self.device, non_blocking=True)                                      # :411
                     lbls = lbls.to(self.device, non_blocking=True)                                      # :412
+                    if self.msms:                                                                       # :413-425
+                        imgs = apply_msms(imgs, lbls, self.msms, "train", nominal)
                     opt.zero_grad()                                                                     # :428
                     if self.graph_steps and world == 1 and graphed is None:
                         from ..graph import GraphedStep
@@ -392,6 +404,7 @@ class ADTrainer(ABC):
     def eval_cls(self, model: torch.nn.Module, ds, cls: int, clsstr: str, seed: int):
         """forward-only scoring of the test split, `ad_trainer.py:473-550`"""
         model = model.to(self.device).eval()
+        self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
         self._normalize_hook(model, ds)
         center = self.center
@@ -402,6 +415,8 @@ class ADTrainer(ABC):
         try:
             for batch in loader:
                 imgs, lbls = batch[0].to(self.device), batch[1]
+                if self.msms:                                                                           # :501-505
+                    imgs = apply_msms(imgs, lbls, self.msms, "test", nominal)
                 with torch.no_grad():
                     feats = model(imgs)
                 ep_scores.append(self.compute_anomaly_score(feats, center, inputs=imgs, nominal_label=nominal))

@@ -517,6 +517,28 @@ int eoe_color_jitter_u8(const uint8_t* src, int64_t n_src, const int32_t* idx, c
                         int32_t* gray_mean_scratch, uint8_t* dst, int n, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Multi-scale modes (MSM): the reference's label-conditioned input filters (utils/transformations.py: GpuDFTLowPassFilter,
+ * GpuDFTHighPassFilter with their MinMaxNorm, Blur = kornia gaussian_blur2d with reflect borders) on fp32 NCHW images in the
+ * [0, 1] pixel scale.  magnitude <= 0 is a bit copy.  lpf / hpf need square images; blur takes k = max(min(2*int(m/2) + 1,
+ * 2*(W/2) - 1), 3) taps, sigma = m.
+ *   eoe_msm_operator   HOST helper, fp64: the 1-D operator G of lpf (A) / hpf (B) for side n at `magnitude` (e = min(m, n/2)).
+ *                      rank_limited = 0: re / im are the dense n x n G (row-major), *cols_out = n, cs_out = {0, 1}.
+ *                      rank_limited = 1: G = cs_out[0] I + cs_out[1] U U^H; re / im are U, n x r row-major, *cols_out = r
+ *                      (r <= n/2).  re == NULL or im == NULL: only *cols_out / cs_out (either may be NULL).
+ *   eoe_msm_workspace  which operator form eoe_msm_filter reads (EOE_MSM_FORM_*) and the workspace bytes it needs
+ *   eoe_msm_filter     y[i] = filter(x[i]) for rows[i] != 0 (rows: n_img uint8 on the DEVICE, NULL = every row), y[i] = x[i] bit
+ *                      for bit otherwise; out of place.  oper (DEVICE, fp32): FORM_DENSE = [Re G | Im G] as two n x n blocks;
+ *                      FORM_RANK = [Ut (n x 2r) | Ut^T (2r x n)] with Ut[j] = (Re U[j][0..r), Im U[j][0..r)); FORM_NONE: unused.
+ *                      The workspace is caller-owned device memory; launches go to `stream`.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { EOE_MSM_LPF = 1, EOE_MSM_HPF = 2, EOE_MSM_BLUR = 3 };
+enum { EOE_MSM_FORM_NONE = 0, EOE_MSM_FORM_DENSE = 1, EOE_MSM_FORM_RANK = 2 };
+int eoe_msm_operator(int op, int n, int magnitude, int rank_limited, double* re, double* im, int* cols_out, double* cs_out);
+int eoe_msm_workspace(int op, int n_img, int C, int H, int W, int magnitude, int* form_out, size_t* bytes_out);
+int eoe_msm_filter(int op, const float* x, float* y, const uint8_t* rows, int n_img, int C, int H, int W, int magnitude,
+                   const float* oper, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Data-parallel exchange (new -- the reference is single-device, main/__init__.py:110-114): gradient
  * SUM all-reduce and score / label all-gather over RCCL on xGMI, one process per GPU.  RCCL is bound at run time (the librccl
  * already in the process, else the system one); without it these return EOE_ERR_UNSUPPORTED and nothing else is affected.
