@@ -216,6 +216,9 @@ SIGNATURES = {
     "eoe_msm_operator": [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int), _vp],
     "eoe_msm_workspace": [C.c_int] * 6 + [C.POINTER(C.c_int), C.POINTER(_sz)],
     "eoe_msm_filter": [C.c_int, _vp, _vp, _vp] + [C.c_int] * 5 + [_vp, _vp, _sz, _vp],
+    "eoe_msm_sharpen_u8": [_vp, _vp, _vp] + [C.c_int] * 4 + [_f32, C.c_int, C.c_int, _vp],
+    "eoe_msm_sharpen_f32": [_vp, _vp, _vp] + [C.c_int] * 4 + [_f32, C.c_int, C.c_int, _vp],
+    "eoe_crop_flip_u8": [_vp, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
     "eoe_comm_destroy": [_vp],

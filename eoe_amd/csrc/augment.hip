@@ -21,6 +21,18 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     return z ^ (z >> 31);
 }
 
+// the source pixel (3 bytes) of output pixel (y, x) of batch slot b, NULL in the zero padding
+__device__ __forceinline__ const uint8_t* crop_flip_src(const uint8_t* __restrict__ src, const int32_t* __restrict__ params, int b, int y,
+                                                        int x, int Hs, int Ws, int Wo, int flip_first) {
+    const int idx = params[b * 4 + 0], top = params[b * 4 + 1], left = params[b * 4 + 2], flip = params[b * 4 + 3];
+    const int sy = top + y;
+    int sx;
+    if (flip_first) sx = flip ? Ws - 1 - (left + x) : left + x;          // flip the source, then crop
+    else sx = left + (flip ? Wo - 1 - x : x);                            // crop, then flip the crop
+    if (sy < 0 || sy >= Hs || sx < 0 || sx >= Ws) return nullptr;
+    return src + (((size_t)idx * Hs + sy) * Ws + sx) * 3;
+}
+
 // one thread per output pixel (img, y, x): 3 source bytes -> 3 floats in the 3 NCHW planes (coalesced along x)
 __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ params,
                                                       const float* __restrict__ mean, const float* __restrict__ stdv,
@@ -29,14 +41,9 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
     const size_t total = (size_t)n * Ho * Wo;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % Wo), y = (int)((i / Wo) % Ho), b = (int)(i / ((size_t)Wo * Ho));
-        const int idx = params[b * 4 + 0], top = params[b * 4 + 1], left = params[b * 4 + 2], flip = params[b * 4 + 3];
-        const int sy = top + y;
-        int sx;
-        if (flip_first) sx = flip ? Ws - 1 - (left + x) : left + x;          // flip the source, then crop
-        else sx = left + (flip ? Wo - 1 - x : x);                            // crop, then flip the crop
+        const uint8_t* p = crop_flip_src(src, params, b, y, x, Hs, Ws, Wo, flip_first);
         float v[3] = {0.f, 0.f, 0.f};                                        // RandomCrop pads with 0
-        if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) {
-            const uint8_t* p = src + (((size_t)idx * Hs + sy) * Ws + sx) * 3;
+        if (p) {
             v[0] = (float)p[0]; v[1] = (float)p[1]; v[2] = (float)p[2];
         }
 #pragma unroll
@@ -70,6 +77,34 @@ extern "C" int eoe_augment_batch(const uint8_t* src, int64_t n_src, int Hs, int 
     hipLaunchKernelGGL(augment_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, params, mean, stdv, out, n, Hs, Ws,
                        Ho, Wo, flip_first, noise_std, (unsigned long long)seed);
     EOE_CHECK_LAUNCH("augment_batch");
+    return 0;
+}
+
+// the crop / flip of eoe_augment_batch alone, uint8 NHWC out: the PIL-stage image that a uint8 filter (the sharpen MSM) sees
+// between the reference's RandomCrop / RandomHorizontalFlip and ToTensor
+namespace {
+__global__ __launch_bounds__(256) void crop_flip_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ params,
+                                                        uint8_t* __restrict__ out, int n, int Hs, int Ws, int Ho, int Wo, int flip_first) {
+    const size_t total = (size_t)n * Ho * Wo;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wo), y = (int)((i / Wo) % Ho), b = (int)(i / ((size_t)Wo * Ho));
+        const uint8_t* p = crop_flip_src(src, params, b, y, x, Hs, Ws, Wo, flip_first);
+        uint8_t* o = out + i * 3;
+        o[0] = p ? p[0] : 0; o[1] = p ? p[1] : 0; o[2] = p ? p[2] : 0;
+    }
+}
+}  // namespace
+
+extern "C" int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, uint8_t* out, int n, int Ho,
+                                int Wo, int flip_first, void* stream) {
+    EOE_CHECK_ARG(src && params && out && n_src > 0 && n > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "crop_flip_u8: bad args");
+    EOE_CHECK_ARG((const void*)src != (const void*)out, "crop_flip_u8: out must not alias src");
+    ProfScope ps("crop_flip_u8", 0, 6.0 * n * Ho * Wo, stream);
+    size_t g = ((size_t)n * Ho * Wo + 255) / 256;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(crop_flip_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, params, out, n, Hs, Ws, Ho, Wo,
+                       flip_first);
+    EOE_CHECK_LAUNCH("crop_flip_u8");
     return 0;
 }
 

@@ -126,6 +126,21 @@ def augment_batch(src_u8, params, out_hw, mean=None, std=None, flip_first=True, 
     return out
 
 
+def crop_flip_u8(src_u8, params, out_hw, flip_first=True):
+    """the crop / flip of augment_batch alone (`eoe_crop_flip_u8`: same params, zero padding, both flip orders): uint8 NHWC
+    [n, Ho, Wo, 3], the PIL image the reference's uint8 transforms see between RandomCrop / RandomHorizontalFlip and ToTensor"""
+    from ._lib import check, lib
+    if not (src_u8.is_cuda and params.is_cuda):
+        raise RuntimeError("crop_flip_u8 needs GPU tensors (there is no CPU fallback)")
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.shape[3] == 3 and src_u8.is_contiguous()
+    assert params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous()
+    n, (Ho, Wo) = params.shape[0], out_hw
+    out = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=src_u8.device)
+    check(lib.eoe_crop_flip_u8(src_u8.data_ptr(), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], params.data_ptr(), out.data_ptr(),
+                               n, Ho, Wo, 1 if flip_first else 0, torch.cuda.current_stream().cuda_stream), "eoe_crop_flip_u8")
+    return out
+
+
 def _resize_tables(in_size, out_size, filt, device):
     """Pillow's filter taps for one axis from the library's host helper, uploaded once"""
     import ctypes as C
@@ -256,6 +271,30 @@ class ResidentImageSource:
     def _norm_args(self):
         return (None, None) if getattr(self, "_defer", False) else (self.mean, self.std)
 
+    def pre_tensor_msms(self, msms):
+        """claim the train sharpen MSMs: the source then applies them where the reference does, to the uint8 crop / flip output
+        before ToTensor and the noise (`datasets/cifar.py:99-118`): per half, crop_flip_u8 -> sharpen_u8 -> augment_batch with
+        identity params and the same seed (the noise depends only on seed, slot and element, so it is unchanged).  Returns the
+        claimed MSMs, which the trainer then leaves out of the step batch's apply_msms; test batches (centre crops, no noise)
+        stay with apply_msms."""
+        self._pre_msms = [m for m in msms if m.transform_str == "sharpen" and m.ds_part_str in ("train_nominal", "train_oe")]
+        return list(self._pre_msms)
+
+    def _augment_half(self, src, p, nominal, mean, std, seed):
+        """one half of a step batch: augment_batch, or with claimed sharpen MSMs for this half the reference's order"""
+        ops = [m for m in getattr(self, "_pre_msms", ()) if (m.ds_part_str == "train_nominal") == nominal]
+        if not ops or p.shape[0] == 0:
+            return augment_batch(src, p, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, seed)
+        from .msm import sharpen_percent, sharpen_u8
+        u8 = crop_flip_u8(src, p, (self.crop, self.crop), self.flip_first)
+        for m in ops:
+            if m.magnitude is None:
+                raise ValueError(f"MSM {m} has no magnitude set")
+            u8 = sharpen_u8(u8, sharpen_percent(m.magnitude))
+        ident = torch.zeros_like(p)
+        ident[:, 0] = torch.arange(p.shape[0], dtype=torch.int32, device=p.device)
+        return augment_batch(u8, ident, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, seed)
+
     def _params(self, idx, Hs, Ws):
         n = len(idx)
         top = torch.randint(-self.padding, Hs + self.padding - self.crop + 1, (n,), generator=self._g)
@@ -291,8 +330,8 @@ class ResidentImageSource:
                 pn[:, 0] = torch.arange(len(ni), dtype=torch.int32, device=dev)
                 po[:, 0] = torch.arange(len(oi), dtype=torch.int32, device=dev)
             mean, std = self._norm_args()
-            xn = augment_batch(src_n, pn, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, 2 * seed)
-            xo = augment_batch(src_o, po, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, 2 * seed + 1)
+            xn = self._augment_half(src_n, pn, True, mean, std, 2 * seed)
+            xo = self._augment_half(src_o, po, False, mean, std, 2 * seed + 1)
             lbls = torch.cat([torch.full((len(ni),), self.nominal_label, dtype=torch.int64),
                               torch.full((len(oi),), self.anomalous_label, dtype=torch.int64)])
             yield torch.cat([xn, xo]), lbls, torch.cat([ni, oi + n_full])      # OE indices offset by the FULL normal set (bases.py:596)

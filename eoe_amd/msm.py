@@ -1,7 +1,9 @@
 """Multi-scale modes (MSM), the reference's frequency-analysis filters (`src/eoe/datasets/__init__.py:157-221,287-309`,
 `utils/transformations.py`): a label-conditioned lpf / hpf / blur applied to the step batch on the device, after the CPU chain
-(crop, flip, ToTensor, noise) and before Normalize (`training/ad_trainer.py:413-425,501-505`).  The filters are the HIP
-kernels of csrc/msm.hip (`eoe_msm_filter`); `sharpen` is Pillow's UnsharpMask on host images and is not built."""
+(crop, flip, ToTensor, noise) and before Normalize (`training/ad_trainer.py:413-425,501-505`), and `sharpen`, Pillow's
+UnsharpMask, which the reference runs on the uint8 PIL image between the PIL augmentations and ToTensor (`datasets/cifar.py:99-118`).
+The filters are the HIP kernels of csrc/msm.hip (`eoe_msm_filter`) and csrc/sharpen.hip (`eoe_msm_sharpen_u8` / `_f32`, byte-exact
+with Pillow); sharpen has no host path, so it needs a GPU device."""
 import ctypes as C
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -11,7 +13,8 @@ import torch
 
 TRANSFORMS = ("blur", "sharpen", "hpf", "lpf")                                    # utils/transformations.py:20
 DS_PARTS = {"train_nominal": 0, "train_oe": 1, "test_nominal": 2, "test_anomalous": 3}   # datasets/__init__.py:150-154
-GPU_OPS = ("lpf", "hpf", "blur")
+GPU_OPS = ("lpf", "hpf", "blur")                                                  # fp32 filters (msm_filter)
+SHARPEN_RADIUS, SHARPEN_THRESHOLD = 2.0, 3                                        # ImageFilter.UnsharpMask defaults
 
 
 class MSM:
@@ -47,11 +50,21 @@ class MSM:
         return res
 
 
-def check_supported(msms: Sequence[MSM]):
+def check_supported(msms: Sequence[MSM], device=None):
+    """lpf / hpf / blur run anywhere msm_filter runs; sharpen only on a GPU device (there is no host path).  device None: not
+    checked here (apply_msms checks the batch's device)"""
     for m in msms:
-        if m.transform_str not in GPU_OPS:
-            raise NotImplementedError(f"MSM transform {m.transform_str!r} ({m}) is not built: sharpen is Pillow's UnsharpMask on host "
-                                      "images; lpf, hpf and blur run on the device")
+        if m.transform_str == "sharpen":
+            if device is not None and torch.device(device).type != "cuda":
+                raise NotImplementedError(f"MSM transform 'sharpen' ({m}) needs a GPU device: Pillow's UnsharpMask is built as a HIP "
+                                          f"kernel only, with no host path (device {device})")
+        elif m.transform_str not in GPU_OPS:
+            raise NotImplementedError(f"MSM transform {m.transform_str!r} ({m}) is not built")
+
+
+def sharpen_percent(magnitude) -> int:
+    """PilUnsharpMask's percent (transformations.py:120)"""
+    return int(magnitude * 100)
 
 
 def blur_taps_k(sigma: float, width: int) -> int:
@@ -118,6 +131,9 @@ def msm_filter(x: torch.Tensor, op: str, magnitude: int, rows: Optional[torch.Te
     """y = op(x) on the rows selected by `rows` (bool / uint8 mask of x.shape[0], None = all), bit copies elsewhere; x fp32
     NCHW in the [0, 1] pixel scale, on the GPU.  Out of place: x is not modified."""
     from ._lib import check, lib
+    if op == "sharpen":
+        raise ValueError("msm_filter: sharpen is not an fp32 filter (Pillow's UnsharpMask on uint8 images); use msm_sharpen or "
+                         "sharpen_u8")
     if op not in _OPS:
         raise ValueError(f"msm_filter: unknown op {op!r}; known: {tuple(_OPS)}")
     if not x.is_cuda:
@@ -144,6 +160,54 @@ def msm_filter(x: torch.Tensor, op: str, magnitude: int, rows: Optional[torch.Te
     return y
 
 
+def _rows_arg(rows, n_img, device):
+    if rows is None:
+        return None
+    r = rows.to(device=device, dtype=torch.uint8).contiguous()
+    assert r.shape == (n_img,)
+    return r
+
+
+def msm_sharpen(x: torch.Tensor, magnitude, rows: Optional[torch.Tensor] = None, radius: float = SHARPEN_RADIUS,
+                threshold: int = SHARPEN_THRESHOLD) -> torch.Tensor:
+    """the reference's PilUnsharpMask(magnitude) on fp32 NCHW batches in [0, 1] on the GPU (`eoe_msm_sharpen_f32`): sharpens
+    q = clamp(rint(x * 255)) and returns q' / 255, bit-exact with ToTensor(Pillow(q)) for batches on the k / 255 grid.  Rows as in
+    msm_filter; magnitude 0 is a bit copy; out of place."""
+    from ._lib import check, lib
+    if not x.is_cuda:
+        raise RuntimeError("msm_sharpen needs a GPU tensor (there is no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 4
+    x = x.contiguous()
+    n_img, ch, h, w = x.shape
+    y = torch.empty_like(x)
+    if n_img == 0:
+        return y
+    r = _rows_arg(rows, n_img, x.device)
+    check(lib.eoe_msm_sharpen_f32(x.data_ptr(), y.data_ptr(), None if r is None else r.data_ptr(), n_img, ch, h, w, float(radius),
+                                  sharpen_percent(magnitude), int(threshold), torch.cuda.current_stream(x.device).cuda_stream),
+          "eoe_msm_sharpen_f32")
+    return y
+
+
+def sharpen_u8(imgs: torch.Tensor, percent: int, rows: Optional[torch.Tensor] = None, radius: float = SHARPEN_RADIUS,
+               threshold: int = SHARPEN_THRESHOLD) -> torch.Tensor:
+    """Pillow's `ImageFilter.UnsharpMask(radius, percent, threshold)` on uint8 NHWC images [n, H, W, C] (C = 1 or 3) on the GPU,
+    byte-exact (`eoe_msm_sharpen_u8`); rows as in msm_filter; out of place"""
+    from ._lib import check, lib
+    if not imgs.is_cuda:
+        raise RuntimeError("sharpen_u8 needs a GPU tensor (there is no CPU fallback)")
+    assert imgs.dtype == torch.uint8 and imgs.dim() == 4
+    imgs = imgs.contiguous()
+    n_img, h, w, ch = imgs.shape
+    out = torch.empty_like(imgs)
+    if n_img == 0:
+        return out
+    r = _rows_arg(rows, n_img, imgs.device)
+    check(lib.eoe_msm_sharpen_u8(imgs.data_ptr(), out.data_ptr(), None if r is None else r.data_ptr(), n_img, h, w, ch, float(radius),
+                                 int(percent), int(threshold), torch.cuda.current_stream(imgs.device).cuda_stream), "eoe_msm_sharpen_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------ routing
 def routing(msms: Sequence[MSM], split: str) -> List[Tuple[str, int, bool, bool]]:
     """(op, magnitude, on nominal rows, on anomalous rows) in list order, as `load_dataset` builds the conditional transforms
@@ -161,17 +225,17 @@ def routing(msms: Sequence[MSM], split: str) -> List[Tuple[str, int, bool, bool]
 
 def apply_msms(imgs: torch.Tensor, lbls: torch.Tensor, msms: Sequence[MSM], split: str = "train", nominal_label: int = 0) -> torch.Tensor:
     """the MSMs of `split` on a step batch ([normal | OE] rows for train, labelled test rows for test); returns `imgs` itself when
-    no MSM applies, a new tensor otherwise"""
+    no MSM applies, a new tensor otherwise.  sharpen runs as msm_sharpen (percent = int(magnitude * 100)) on the fp32 batch"""
     steps = routing(msms, split)
     if not steps:
         return imgs
-    check_supported(msms)
+    check_supported(msms, imgs.device)
     nominal = lbls.to(imgs.device) == nominal_label
     for op, mag, on_nom, on_anom in steps:
         if mag is None:
             raise ValueError(f"MSM {op} has no magnitude set")
         rows = None if (on_nom and on_anom) else (nominal if on_nom else ~nominal)
-        imgs = msm_filter(imgs, op, mag, rows)
+        imgs = msm_sharpen(imgs, mag, rows) if op == "sharpen" else msm_filter(imgs, op, mag, rows)
     return imgs
 
 
@@ -209,6 +273,44 @@ def blur_np(x: np.ndarray, sigma: float) -> np.ndarray:
     h, w = x.shape[-2:]
     tmp = sum(g[q] * xp[:, :, :, q:q + w] for q in range(k))
     return sum(g[q] * tmp[:, :, q:q + h, :] for q in range(k))
+
+
+def sharpen_box(radius: float = SHARPEN_RADIUS) -> Tuple[int, int, int]:
+    """(r, ww, fw) of Pillow's box passes for a Gaussian radius (_gaussian_blur_radius with 3 passes, ImagingHorizontalBoxBlur), in
+    Pillow's float / double / uint32 arithmetic"""
+    f = np.float32
+    s2 = f(f(radius) * f(radius) / f(3))
+    big_l = f(math.sqrt(12.0 * float(s2) + 1.0))
+    small_l = f(math.floor((float(big_l) - 1.0) / 2.0))
+    a = f(f(f(2) * small_l + f(1)) * f(small_l * f(small_l + f(1)) - f(3) * s2))
+    a = f(a / f(f(6) * f(s2 - f(small_l + f(1)) * f(small_l + f(1)))))
+    big_r = f(small_l + a)
+    r = int(big_r)
+    ww = int(f(f(1 << 24) / f(big_r * f(2) + f(1))))
+    fw = (((1 << 24) - (2 * r + 1) * ww) & 0xFFFFFFFF) // 2
+    return r, ww, fw
+
+
+def unsharp_np(u8: np.ndarray, percent: int, radius: float = SHARPEN_RADIUS, threshold: int = SHARPEN_THRESHOLD) -> np.ndarray:
+    """numpy restatement of Pillow's ImageFilter.UnsharpMask on uint8 images [..., H, W, C] (libImaging/UnsharpMask.c over
+    BoxBlur.c: 3 horizontal + 3 vertical box passes with replicated edges, each rounded to uint8; then |d| > threshold ?
+    clamp(src + trunc(d * percent / 100)) : src), byte-exact"""
+    assert u8.dtype == np.uint8 and u8.ndim >= 3
+    r, ww, fw = sharpen_box(radius)
+
+    def box(a, axis):
+        n = a.shape[axis]
+        t = lambda k: np.take(a, np.clip(np.arange(n) + k, 0, n - 1), axis=axis).astype(np.uint64)
+        v = (sum(t(k) for k in range(-r, r + 1)) * ww + (t(-r - 1) + t(r + 1)) * fw) & 0xFFFFFFFF
+        return (((v + (1 << 23)) & 0xFFFFFFFF) >> 24).astype(np.uint8)
+
+    b = u8
+    for axis in (-2, -2, -2, -3, -3, -3):
+        b = box(b, axis)
+    src = u8.astype(np.int64)
+    dp = (src - b) * int(percent)
+    out = np.clip(src + np.sign(dp) * (np.abs(dp) // 100), 0, 255)
+    return np.where(np.abs(src - b) > threshold, out, src).astype(np.uint8)
 
 
 def torch_fft_filter(x: torch.Tensor, op: str, magnitude: int) -> torch.Tensor:

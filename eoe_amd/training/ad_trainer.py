@@ -13,7 +13,9 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
   * optional data parallelism (one process per GPU): each rank trains on its rows of every step batch,
     loss = sum(local) / global batch, gradients summed over RCCL, scores/labels all-gathered for the AUC;
   * multi-scale modes (`msms`, eoe_amd.msm): lpf / hpf / blur run as HIP kernels on the device batch after `.to(device)`
-    and before the encoder's fused Normalize (:413-425 train, :501-505 test); `sharpen` (Pillow on host images) is not built.
+    and before the encoder's fused Normalize (:413-425 train, :501-505 test); so does `sharpen` (Pillow's UnsharpMask, a HIP
+    kernel on the [0, 1] batch quantised to uint8; GPU devices only), unless the source applies it to its uint8 images before
+    ToTensor and the noise as the reference does (ResidentImageSource.pre_tensor_msms).
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -119,7 +121,8 @@ class ADTrainer(ABC):
         # train_imagenet.py:16), True / False = forced.  The ViT has no BatchNorm and meets the bar in its 16-bit mode.
         self.exact_bn = exact_bn
         self.msms = list(msms or ())
-        check_supported(self.msms)          # sharpen raises NotImplementedError
+        check_supported(self.msms, self.device)          # sharpen on a CPU device raises NotImplementedError
+        self._step_msms = self.msms                         # the train MSMs left to the step batch (_msm_source)
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -234,6 +237,10 @@ class ADTrainer(ABC):
         (ResidentImageSource) hands (mean, std) to the encoder's fused normalise instead"""
         if self.msms and hasattr(ds, "defer_normalize"):
             ds.defer_normalize(True)
+        # a source that applies some train MSMs itself, before ToTensor (ResidentImageSource: sharpen), claims them; told every
+        # time, so that a source shared between trainers never keeps an earlier trainer's claim
+        claimed = ds.pre_tensor_msms(self.msms) if hasattr(ds, "pre_tensor_msms") else []
+        self._step_msms = [m for m in self.msms if not any(m is c for c in claimed)]
 
     def _normalize_hook(self, model, ds):
         """install the (mean, std) of the normal class on an encoder that fuses it; returns a fallback callable for
@@ -343,7 +350,7 @@ class ADTrainer(ABC):
                     imgs = imgs.to(self.device, non_blocking=True)                                      # :411
                     lbls = lbls.to(self.device, non_blocking=True)                                      # :412
                     if self.msms:                                                                       # :413-425
-                        imgs = apply_msms(imgs, lbls, self.msms, "train", nominal)
+                        imgs = apply_msms(imgs, lbls, self._step_msms, "train", nominal)
                     opt.zero_grad()                                                                     # :428
                     if self.graph_steps and world == 1 and graphed is None:
                         from ..graph import GraphedStep

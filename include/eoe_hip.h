@@ -537,6 +537,22 @@ int eoe_msm_operator(int op, int n, int magnitude, int rank_limited, double* re,
 int eoe_msm_workspace(int op, int n_img, int C, int H, int W, int magnitude, int* form_out, size_t* bytes_out);
 int eoe_msm_filter(int op, const float* x, float* y, const uint8_t* rows, int n_img, int C, int H, int W, int magnitude,
                    const float* oper, void* workspace, size_t workspace_bytes, void* stream);
+/* The sharpen MSM: Pillow's ImageFilter.UnsharpMask(radius, percent, threshold) (the reference's PilUnsharpMask: radius 2,
+ * percent int(magnitude * 100), threshold 3), byte-exact with Pillow: 3 horizontal + 3 vertical box passes with replicated edges
+ * on uint8, then |d| > threshold ? clamp(src + d * percent / 100) : src per pixel with d = src - blurred.  One launch; rows as in
+ * eoe_msm_filter (NULL = every image, unselected images bit copies); percent == 0 is a bit copy; out of place; C is 1 or 3;
+ * planes of at most 65536 pixels; 0 <= radius <= 256, 0 <= percent <= 2^20.
+ *   eoe_msm_sharpen_u8   uint8 NHWC [n_img, H, W, C] (PIL images, resident sets)
+ *   eoe_msm_sharpen_f32  fp32 NCHW [n_img, C, H, W] in [0, 1]: sharpens q = clamp(rint(x * 255)) and writes q' / 255.0f
+ *                        (ToTensor's bits: exact for batches on the k / 255 grid)
+ *   eoe_crop_flip_u8     the crop / flip of eoe_augment_batch (same params, zero padding, both flip orders) on its own:
+ *                        uint8 NHWC [n, Ho, Wo, 3] out, the image a PIL-stage filter sees before ToTensor */
+int eoe_msm_sharpen_u8(const uint8_t* src, uint8_t* dst, const uint8_t* rows, int n_img, int H, int W, int C, float radius,
+                       int percent, int threshold, void* stream);
+int eoe_msm_sharpen_f32(const float* x, float* y, const uint8_t* rows, int n_img, int C, int H, int W, float radius, int percent,
+                        int threshold, void* stream);
+int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, uint8_t* out, int n, int Ho, int Wo,
+                     int flip_first, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Data-parallel exchange (new -- the reference is single-device, main/__init__.py:110-114): gradient
