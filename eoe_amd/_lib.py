@@ -100,6 +100,17 @@ class VitBlockFwdArgs(C.Structure):
                 ("stats1", _vp), ("stats2", _vp), ("cls_only", _i32), ("nt_sk_workspace", _vp), ("nt_sk_workspace_bytes", _i64)]
 
 
+class ClipTextFwdArgs(C.Structure):
+    _fields_ = [("n", _i32), ("L", _i32), ("D", _i32), ("heads", _i32), ("layers", _i32), ("vocab", _i32), ("embed_dim", _i32),
+                ("dtype", _i32), ("eps", _f32), ("tok_i64", _i32), ("tokens", _vp), ("token_embedding", _vp), ("positional_embedding", _vp),
+                ("ln1_g", C.POINTER(_vp)), ("ln1_b", C.POINTER(_vp)), ("ln2_g", C.POINTER(_vp)), ("ln2_b", C.POINTER(_vp)),
+                ("b_in", C.POINTER(_vp)), ("b_out", C.POINTER(_vp)), ("b_fc", C.POINTER(_vp)), ("b_proj", C.POINTER(_vp)),
+                ("w_in", C.POINTER(_vp)), ("w_out", C.POINTER(_vp)), ("w_fc", C.POINTER(_vp)), ("w_proj", C.POINTER(_vp)),
+                ("lnf_g", _vp), ("lnf_b", _vp), ("proj_t", _vp),
+                ("x0", _vp), ("x1", _vp), ("xn", _vp), ("qkv", _vp), ("att", _vp), ("hact", _vp), ("stats", _vp), ("eot16", _vp),
+                ("out", _vp), ("nt_sk_workspace", _vp), ("nt_sk_workspace_bytes", _i64)]
+
+
 class RedJob(C.Structure):
     _fields_ = [("part", _vp), ("R", _i32), ("N", _i32), ("seg", _i32), ("blocked", _i32), ("out", _vp * 3)]
 
@@ -153,6 +164,10 @@ SIGNATURES = {
     "eoe_cast": [_vp, _vp, _sz, C.c_int, _vp],
     "eoe_attn_fwd": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_attn_bwd": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_attn_causal_fwd": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_clip_token_embed": [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_clip_eot_ln": [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, C.c_int, _vp],
+    "eoe_clip_text_fwd": [C.POINTER(ClipTextFwdArgs), _vp],
     "eoe_hsc_fwd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f32, _vp],
     "eoe_hsc_bwd": [_vp, _vp, _i64, _vp, _vp, _vp, C.c_int, C.c_int, _f32, C.c_int, _vp],
     "eoe_hsc_score": [_vp, _vp, C.c_int, C.c_int, _vp],

@@ -16,6 +16,14 @@ from torch import nn
 from .. import ops
 
 
+def is_causal_mask(m) -> bool:
+    """m is CLIP.build_attention_mask()'s additive mask: square, -inf strictly above the diagonal, 0 elsewhere"""
+    if not isinstance(m, torch.Tensor) or m.dim() != 2 or m.shape[0] != m.shape[1] or not m.is_floating_point():
+        return False
+    want = torch.full(m.shape, float("-inf"), dtype=m.dtype, device=m.device).triu_(1)
+    return bool(torch.equal(m, want))
+
+
 class _PackedAttention(nn.Module):
     """parameter container with nn.MultiheadAttention's names: in_proj_weight [3D,D], in_proj_bias [3D],
     out_proj.{weight,bias} (model.py:171)"""
@@ -40,8 +48,11 @@ class ResidualAttentionBlock(nn.Module):
 
     def __init__(self, d_model: int, n_head: int, attn_mask: torch.Tensor = None):
         super().__init__()
-        if attn_mask is not None:
-            raise NotImplementedError("attention masks belong to the text tower, which is out of scope")
+        # the one mask the kernels know: CLIP.build_attention_mask's causal mask of the text tower (model.py:284-290), which runs as a whole
+        # through CLIP.encode_text
+        self.causal = attn_mask is not None
+        if self.causal and not is_causal_mask(attn_mask):
+            raise NotImplementedError("only the causal mask of CLIP.build_attention_mask (-inf strictly above the diagonal) is supported")
         if d_model != 64 * n_head:
             raise NotImplementedError("the attention kernel is written for head dim 64")
         self.n_head = n_head
@@ -53,7 +64,7 @@ class ResidualAttentionBlock(nn.Module):
             ("c_proj", nn.Linear(d_model * 4, d_model)),
         ]))
         self.ln_2 = nn.LayerNorm(d_model)
-        self.attn_mask = None
+        self.attn_mask = attn_mask
 
     def _params(self):
         return (self.ln_1.weight, self.ln_1.bias, self.attn.in_proj_weight, self.attn.in_proj_bias,
@@ -66,6 +77,8 @@ class ResidualAttentionBlock(nn.Module):
         return ops.VitBlockFunction.apply(x2d, n, self.n_head, *self._params(), cls_only)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.causal:
+            raise NotImplementedError("a causal (text-tower) block runs only inside CLIP.encode_text")
         n, L, D = x.shape
         return self.forward_tokens(x.reshape(n * L, D).float(), n).reshape(n, L, D)
 

@@ -223,6 +223,13 @@ def attn_bwd(qkv, dout, dqkv, n, L, heads, dbias=None):
     return dqkv
 
 
+def attn_causal_fwd(qkv, out, n, L, heads):
+    """causal attention of CLIP's text tower (key j reaches query i only for j <= i), same layout as attn_fwd; 1 <= L <= 128"""
+    _chk(qkv, out)
+    check(lib.eoe_attn_causal_fwd(_p(qkv), _p(out), n, L, heads, dtype_code(qkv.dtype), _stream()), "eoe_attn_causal_fwd")
+    return out
+
+
 def patchify(x, patch, mean=None, std=None, dtype=None):
     _chk(x, mean, std)
     dtype = dtype or _compute_dtype
@@ -1685,3 +1692,57 @@ class BnActFunction(torch.autograd.Function):
                                       C, 1, 0, 1 if ctx.training else 0, 0, 0.01, dtype_code(_compute_dtype), _stream()),
               "eoe_bn_act_pool_bwd")
         return dy, dg, db, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ CLIP text tower (forward only)
+def check_token_ids(tokens: torch.Tensor, vocab: int):
+    """the token matrix the text tower accepts: [n, L] int64 / int32 ids in [0, vocab) (a kernel cannot report a bad id)"""
+    if not isinstance(tokens, torch.Tensor) or tokens.dim() != 2 or tokens.dtype not in (torch.int64, torch.int32):
+        raise ValueError("text tokens must be an int64 / int32 tensor [n, context_length] (clip.tokenize)")
+    if tokens.numel() and (int(tokens.min()) < 0 or int(tokens.max()) >= vocab):
+        raise ValueError(f"token ids must lie in [0, {vocab}), got [{int(tokens.min())}, {int(tokens.max())}]")
+
+
+def clip_text_fwd(tokens, blocks, heads, token_embedding, positional_embedding, ln_final, text_projection):
+    """CLIP.encode_text (clip/model.py:343-356) in one C call (eoe_clip_text_fwd): tokens [n, L] -> fp32 text features [n, embed_dim].
+    `blocks`: the ResidualAttentionBlocks of the text transformer.  No autograd."""
+    D = token_embedding.shape[1]
+    check_token_ids(tokens, token_embedding.shape[0])
+    _chk(token_embedding)
+    n, L = tokens.shape
+    if L > positional_embedding.shape[0]:
+        raise ValueError(f"{L} tokens per prompt, but the positional embedding has {positional_embedding.shape[0]} rows")
+    dev = token_embedding.device
+    tok = tokens.to(dev).contiguous()
+    mats = [w for b in blocks for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
+    shadow.refresh(mats + [text_projection])
+    sh = [shadow.get(w, True, True)[0] for w in mats]
+    proj_t = shadow.get(text_projection, True, True)[1]           # [embed_dim, D]
+    f32 = lambda t: t.detach().contiguous().float()              # noqa: E731  (fp32 masters: already contiguous fp32)
+    vec = [[f32(getattr(b, ln).weight) for b in blocks] for ln in ("ln_1", "ln_2")] + \
+          [[f32(getattr(b, ln).bias) for b in blocks] for ln in ("ln_1", "ln_2")]
+    biases = [[f32(x) for x in xs] for xs in zip(*[(b.attn.in_proj_bias, b.attn.out_proj.bias, b.mlp.c_fc.bias, b.mlp.c_proj.bias)
+                                                    for b in blocks])] if blocks else [[], [], [], []]
+    nl = len(blocks)
+    arr = lambda ts: (C.c_void_p * max(nl, 1))(*[_p(t) for t in ts])      # noqa: E731
+    M, E, dt = n * L, text_projection.shape[1], _compute_dtype
+    out = torch.empty((n, E), dtype=torch.float32, device=dev)
+    x0, x1 = torch.empty((M, D), dtype=torch.float32, device=dev), torch.empty((M, D), dtype=torch.float32, device=dev)
+    xn, att = torch.empty((M, D), dtype=dt, device=dev), torch.empty((M, D), dtype=dt, device=dev)
+    qkv, hact = torch.empty((M, 3 * D), dtype=dt, device=dev), torch.empty((M, 4 * D), dtype=dt, device=dev)
+    stats, eot16 = torch.empty((M, 2), dtype=torch.float32, device=dev), torch.empty((n, D), dtype=dt, device=dev)
+    emb, pos = f32(token_embedding), f32(positional_embedding)
+    lnf_g, lnf_b = f32(ln_final.weight), f32(ln_final.bias)
+    sk_ws = nt_sk_workspace(dev)
+    a = _lib.ClipTextFwdArgs()
+    a.n, a.L, a.D, a.heads, a.layers, a.vocab, a.embed_dim = n, L, D, heads, nl, token_embedding.shape[0], E
+    a.dtype, a.eps, a.tok_i64 = dtype_code(dt), 1e-5, 1 if tok.dtype == torch.int64 else 0
+    a.tokens, a.token_embedding, a.positional_embedding = _p(tok), _p(emb), _p(pos)
+    keep = [arr(vec[0]), arr(vec[2]), arr(vec[1]), arr(vec[3])] + [arr(b) for b in biases] + [arr(sh[i::4]) for i in range(4)]
+    (a.ln1_g, a.ln1_b, a.ln2_g, a.ln2_b, a.b_in, a.b_out, a.b_fc, a.b_proj, a.w_in, a.w_out, a.w_fc, a.w_proj) = \
+        [C.cast(k, C.POINTER(C.c_void_p)) for k in keep]
+    a.lnf_g, a.lnf_b, a.proj_t = _p(lnf_g), _p(lnf_b), _p(proj_t)
+    a.x0, a.x1, a.xn, a.qkv, a.att, a.hact, a.stats, a.eot16, a.out = (_p(t) for t in (x0, x1, xn, qkv, att, hact, stats, eot16, out))
+    a.nt_sk_workspace, a.nt_sk_workspace_bytes = _p(sk_ws), sk_ws.numel()
+    check(lib.eoe_clip_text_fwd(C.byref(a), _stream()), "eoe_clip_text_fwd")
+    return out

@@ -1,5 +1,6 @@
 """objective name -> trainer class, as `src/eoe/training/__init__.py:8-11`.  'clip' takes the frozen text features from the
-caller (the text tower is outside the hot path); the autoencoder trainer is not built."""
+caller, or encodes its prompts with an `eoe_amd.models.CLIP` model's text tower given a tokenizer; the autoencoder trainer is not
+built."""
 from .ad_trainer import ADTrainer, NanGradientsError      # noqa: F401
 from .hsc import HSCTrainer
 from .bce import BCETrainer

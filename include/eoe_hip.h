@@ -218,6 +218,50 @@ int eoe_attn_bwd(const void* qkv, const void* dout, void* dqkv, float* dbias, fl
                  int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * CLIP's text tower (clip/model.py:343-356 CLIP.encode_text), forward only (the prompts are encoded once per run, under no_grad,
+ * training/clip.py:59-61).
+ * ---------------------------------------------------------------------------------------------------- */
+/* causal multi-head attention (the -inf-above-the-diagonal mask of CLIP.build_attention_mask, model.py:284-290): key j contributes to
+ * query i only when j <= i.  Same layout as eoe_attn_fwd: qkv 16-bit [n*L, 3*D] (q | k | v, D = heads*64), out 16-bit [n*L, D];
+ * 1 <= L <= 128; fp32 scores and softmax.  Only rows < n*L of qkv are read and of out written. */
+int eoe_attn_causal_fwd(const void* qkv, void* out, int n, int L, int heads, int dtype, void* stream);
+/* token embedding (model.py:345-347): out fp32 [n*L, D] = token_embedding[tok[s, t], :] + positional_embedding[t, :].  tok [n, L] int64
+ * (tok_i64 != 0, what clip.tokenize returns) or int32; token_embedding fp32 [vocab, D], positional_embedding fp32 [>= L, D].  The caller
+ * checks 0 <= id < vocab (a kernel cannot report it; an id outside is clamped into the table). */
+int eoe_clip_token_embed(const void* tok, int tok_i64, const float* token_embedding, const float* positional_embedding, float* out, int n,
+                         int L, int D, int vocab, void* stream);
+/* EOT head (model.py:349-356 before the projection): per sequence s the position t* of its largest token id (the first of equal ones:
+ * text.argmax(dim=-1)), and y 16-bit [n, D] = LayerNorm(x[s*L + t*, :]) with ln_final's gamma / beta (fp32 statistics). */
+int eoe_clip_eot_ln(const float* x, const void* tok, int tok_i64, const float* gamma, const float* beta, void* y, int n, int L, int D,
+                    float eps, int dtype, void* stream);
+/* the whole tower in one call: embedding; per layer LayerNorm-1 -> in_proj (eoe_gemm_nt) -> eoe_attn_causal_fwd -> out_proj + residual
+ * -> LayerNorm-2 -> c_fc + QuickGELU -> c_proj + residual (the chain of eoe_vit_block_fwd); the EOT head; out = eot16 . text_projection.
+ * Nothing is kept for a backward pass. */
+typedef struct {
+    int32_t n, L, D, heads, layers, vocab, embed_dim, dtype;   /* D = 64*heads, 1 <= L <= 128, D % 64 == 0 */
+    float eps;
+    int32_t tok_i64;
+    const void* tokens;                  /* [n, L] int64 / int32 (ids checked by the caller) */
+    const float* token_embedding;        /* fp32 [vocab, D] */
+    const float* positional_embedding;   /* fp32 [>= L, D] */
+    /* per layer: HOST arrays of `layers` device pointers; vectors fp32, matrices 16-bit row-major [out, in] */
+    const float* const* ln1_g; const float* const* ln1_b; const float* const* ln2_g; const float* const* ln2_b;
+    const float* const* b_in; const float* const* b_out; const float* const* b_fc; const float* const* b_proj;
+    const void* const* w_in; const void* const* w_out; const void* const* w_fc; const void* const* w_proj;   /* [3D,D] [D,D] [4D,D] [D,4D] */
+    const float *lnf_g, *lnf_b;          /* ln_final */
+    const void* proj_t;                  /* 16-bit [embed_dim, D] = text_projection^T */
+    /* caller-allocated workspace */
+    float *x0, *x1;                      /* fp32 [n*L, D] residual stream (ping-pong) */
+    void *xn, *qkv, *att, *hact;         /* 16-bit [n*L, D] [n*L, 3D] [n*L, D] [n*L, 4D] */
+    float* stats;                        /* fp32 [n*L, 2] */
+    void* eot16;                         /* 16-bit [n, D] */
+    float* out;                          /* fp32 [n, embed_dim]: the text features */
+    void* nt_sk_workspace;               /* optional: eoe_gemm_args.sk_workspace */
+    int64_t nt_sk_workspace_bytes;
+} eoe_clip_text_fwd_args;
+int eoe_clip_text_fwd(const eoe_clip_text_fwd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * objectives (fused heads)
  * ---------------------------------------------------------------------------------------------------- */
 /* HSC (hsc.py:12-21): f fp32 [n, d]; labels int64 [n]; per sample  dist = sqrt(|f|^2+1)-1,
