@@ -11,7 +11,8 @@
 // columns / sqrt(n): either the kept set (c = 0, s = 1) or its complement (c = 1, s = -1), whichever is smaller, r <= n / 2.
 //   * n <= 32 (CIFAR 32^2, CNN28 28^2): one workgroup per image, the whole image and the dense G in LDS, one launch with the
 //     MinMax fused; fp64 accumulation of fp32 operands.
-//   * larger n (224^2): the rank-limited form as batched fp32 GEMMs through a caller workspace.  With Ut = [Re U | Im U]
+//   * larger n (224^2): the rank-limited form as batched GEMMs (fp32 operands and intermediates, fp64 accumulation) through a
+//     caller workspace.  With Ut = [Re U | Im U]
 //     (n x 2r, real), A1 = Ut^T X, A2 = X Ut, T = A1 Ut and M = [[Trr - Tii, Tri + Tir], [Tir + Tri, Tii - Trr]]:
 //       Re(G X G^T) = c^2 X + cs (Ut A1 + A2 Ut^T) + s^2 Ut M Ut^T
 //     i.e. 10 r n^2 multiply-adds per plane instead of the dense form's 4 n^3.  A final pass (one workgroup per image) applies
@@ -20,7 +21,9 @@
 // reference does.  magnitude <= 0 is the identity: a bit-exact copy, no MinMax.
 //
 // blur.  kornia's gaussian_blur2d(img, (k, k), (sigma, sigma)) with reflect borders: separable, normalised exp(-x^2 / 2 sigma^2)
-// taps, x = arange(k) - k // 2, k = max(min(2*int(sigma/2) + 1, 2*(W//2) - 1), 3); two passes through the workspace.
+// taps, x = arange(k) - k // 2, k = max(min(2*int(sigma/2) + 1, 2*(W//2) - 1), 3); two passes through the workspace.  The taps
+// travel in the kernel arguments, at most BLUR_MAX_TAPS = 223 of them: every k of the rule for images up to 224 wide, in
+// 892 bytes of taps (the whole argument block stays under 1 KiB).
 //
 // Row selection: rows[i] != 0 filters image i, rows[i] == 0 copies it bit for bit; rows == NULL filters every image.  The op
 // is out of place (y must not alias x).
@@ -33,7 +36,7 @@ namespace {
 
 constexpr int SMALL_N = 32;          // largest side of the one-workgroup LDS path
 constexpr int SMALL_C = 3;
-constexpr int BLUR_MAX_TAPS = 129;
+constexpr int BLUR_MAX_TAPS = 223;   // k at W = 224 and sigma >= 222 (the ImageNet driver's 256)
 
 struct BlurTaps { float w[BLUR_MAX_TAPS]; };
 
@@ -97,9 +100,12 @@ __global__ __launch_bounds__(256) void msm_small_kernel(const float* __restrict_
     for (int i = t; i < tot; i += 256) yb[i] = (X[i] - mn) / d;
 }
 
-// ---- batched fp32 GEMM for the rank-limited form -----------------------------------------------------------------------
+// ---- batched GEMM for the rank-limited form: fp32 operands, fp64 accumulation --------------------------------------------
 // C[p] = ax * Xin[p] + ab * A[p] B[p] (+ C[p] when accumulate), A: M x K (lda), B: K x N (ldb), row-major; a stride of 0 shares
-// the operand between planes.  Plane p belongs to image p / C; planes of unselected images are skipped.
+// the operand between planes.  Plane p belongs to image p / C; planes of unselected images are skipped.  The sums run in fp64
+// and the epilogue rounds once to fp32, as msm_small_kernel does: when U holds the DC column (lpf on its kept set, magnitude
+// >= 56 at 224^2), A1 and T carry the plane's column and total sums (T's DC entry is n / 2 for a mean-0.5 image, against
+// outputs of order 1), and fp32 sums put lpf 64 / 100 at about 4x the reference's own fp32 distance from fp64.
 struct GemmB {
     const float* A; const float* B; float* Cm; const float* Xin;
     long long sA, sB, sC, sX;
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(256) void msm_gemm_kernel(GemmB g) {
     const float* B = g.B + p * g.sB;
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
     const int t = threadIdx.x, tx = t % 16, ty = t / 16;
-    float acc[4][4] = {};
+    double acc[4][4] = {};
     for (int k0 = 0; k0 < g.K; k0 += 16) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -133,13 +139,13 @@ __global__ __launch_bounds__(256) void msm_gemm_kernel(GemmB g) {
         __syncthreads();
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
-            float a[4], bv[4];
+            double a[4], bv[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) { a[i] = As[kk][ty * 4 + i]; bv[i] = Bs[kk][tx * 4 + i]; }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], bv[j], acc[i][j]);
+                for (int j = 0; j < 4; ++j) acc[i][j] = fma(a[i], bv[j], acc[i][j]);
         }
         __syncthreads();
     }
@@ -153,11 +159,11 @@ __global__ __launch_bounds__(256) void msm_gemm_kernel(GemmB g) {
         for (int j = 0; j < 4; ++j) {
             const int gn = n0 + tx * 4 + j;
             if (gn >= g.N) continue;
-            float v = g.ab * acc[i][j];
-            if (X) v = fmaf(g.ax, X[(size_t)gm * g.ldx + gn], v);
+            double v = (double)g.ab * acc[i][j];
+            if (X) v += (double)g.ax * X[(size_t)gm * g.ldx + gn];
             float* dst = Cm + (size_t)gm * g.ldc + gn;
             if (g.accumulate) v += *dst;
-            *dst = v;
+            *dst = (float)v;
         }
     }
 }

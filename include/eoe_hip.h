@@ -564,7 +564,7 @@ int eoe_color_jitter_u8(const uint8_t* src, int64_t n_src, const int32_t* idx, c
  * Multi-scale modes (MSM): the reference's label-conditioned input filters (utils/transformations.py: GpuDFTLowPassFilter,
  * GpuDFTHighPassFilter with their MinMaxNorm, Blur = kornia gaussian_blur2d with reflect borders) on fp32 NCHW images in the
  * [0, 1] pixel scale.  magnitude <= 0 is a bit copy.  lpf / hpf need square images; blur takes k = max(min(2*int(m/2) + 1,
- * 2*(W/2) - 1), 3) taps, sigma = m.
+ * 2*(W/2) - 1), 3) taps, sigma = m, and refuses k > 223 (EOE_ERR_UNSUPPORTED; every k of images up to 224 wide is taken).
  *   eoe_msm_operator   HOST helper, fp64: the 1-D operator G of lpf (A) / hpf (B) for side n at `magnitude` (e = min(m, n/2)).
  *                      rank_limited = 0: re / im are the dense n x n G (row-major), *cols_out = n, cs_out = {0, 1}.
  *                      rank_limited = 1: G = cs_out[0] I + cs_out[1] U U^H; re / im are U, n x r row-major, *cols_out = r

@@ -21,6 +21,8 @@ from oracle.fill import fill   # noqa: E402
 REF = "/root/reference/src/eoe"
 SHAPES = {"32": (1, 3, 32, 32), "28": (2, 1, 28, 28), "224": (1, 1, 224, 224)}
 MAGNITUDES = (0, 1, 2, 4, 8, 16, 32)
+# 224^2 also takes the rest of the ImageNet driver's defaults (multiscale_imagenet.py); at 28^2 / 32^2 they clip to n/2 = 16
+MAGNITUDES_BY_SIZE = {"32": MAGNITUDES, "28": MAGNITUDES, "224": MAGNITUDES + (64, 128, 256)}
 
 
 def _stub(name, **attrs):
@@ -58,7 +60,7 @@ def main():
         if size != "224":
             out[f"in64/{size}"] = x32.astype(np.float64)
         for op, cls in (("lpf", T.GpuDFTLowPassFilter), ("hpf", T.GpuDFTHighPassFilter)):
-            for mag in MAGNITUDES:
+            for mag in MAGNITUDES_BY_SIZE[size]:
                 f = cls(types.SimpleNamespace(magnitude=mag))
                 for dt, tag in ((torch.float64, "out64"), (torch.float32, "out32")):
                     y = f(torch.from_numpy(x32).to(dt)).numpy()

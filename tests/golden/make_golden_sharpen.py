@@ -22,7 +22,8 @@ REF = "/root/reference/src/eoe"
 MAGNITUDES = (0, 1, 2, 4, 8, 16, 32)
 # case -> (h, w, c, number of images, magnitudes)
 CASES = {"rgb32": (32, 32, 3, 4, MAGNITUDES), "l28": (28, 28, 1, 4, MAGNITUDES), "rgb3x3": (3, 3, 3, 2, MAGNITUDES),
-         "l5x7": (5, 7, 1, 2, MAGNITUDES), "rgb5x7": (5, 7, 3, 2, MAGNITUDES), "rgb224": (224, 224, 3, 1, (0, 1, 4, 32))}
+         "l5x7": (5, 7, 1, 2, MAGNITUDES), "rgb5x7": (5, 7, 3, 2, MAGNITUDES),
+         "rgb224": (224, 224, 3, 1, (0, 1, 4, 32, 64, 128, 256))}           # 64-256: the ImageNet driver's defaults
 GRID = 4
 
 

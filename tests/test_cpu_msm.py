@@ -126,12 +126,41 @@ def test_numpy_form_matches_golden_fp64(golden):
 
 def test_blur_k_rule_matches_reference_formula():
     from eoe_amd.msm import blur_taps_k
-    for sigma in (0.5, 1, 2, 3, 4, 7, 8, 16, 32, 64, 100):
+    for sigma in (0.5, 1, 2, 3, 4, 7, 8, 16, 32, 64, 100, 128, 256):
         for w in (28, 32, 224):
             k_ref = 2 * int(int(sigma / 2) + 0.5) + 1
             k_ref = max(min(k_ref, 2 * int(int(w / 2) + 0.5) - 1), 3)
             assert blur_taps_k(sigma, w) == k_ref
     assert blur_taps_k(8, 32) == 9 and blur_taps_k(32, 32) == 31 and blur_taps_k(1, 32) == 3
+    assert blur_taps_k(128, 224) == 129 and blur_taps_k(256, 224) == 223 and blur_taps_k(256, 28) == 27
+
+
+def test_blur_workspace_takes_the_imagenet_magnitudes_at_224():
+    """the ImageNet driver's blur magnitudes (multiscale_imagenet.py: up to 256) at 224^2: k = 65, 129 and 223 taps"""
+    from eoe_amd import _lib
+    lib = _lib.lib
+    form, nb = C.c_int(-1), C.c_size_t(1)
+    for sigma in (64, 128, 256):
+        rc = lib.eoe_msm_workspace(3, 4, 3, 224, 224, sigma, C.byref(form), C.byref(nb))
+        assert rc == 0, (sigma, lib.eoe_last_error())
+        assert form.value == 0 and nb.value == 4 * 4 * 3 * 224 * 224, sigma
+
+
+def test_blur_tap_limit_boundary():
+    """the largest k the kernels take (223) is accepted, the next odd k (225: W = 226 at sigma 224) is refused, naming the
+    limit"""
+    from eoe_amd import _lib
+    from eoe_amd.msm import blur_taps_k
+    lib = _lib.lib
+    form, nb = C.c_int(0), C.c_size_t(0)
+    assert blur_taps_k(222, 226) == 223 and blur_taps_k(224, 226) == 225
+    assert lib.eoe_msm_workspace(3, 2, 1, 226, 226, 222, C.byref(form), C.byref(nb)) == 0
+    assert nb.value == 4 * 2 * 226 * 226
+    assert lib.eoe_msm_workspace(3, 2, 1, 226, 226, 224, C.byref(form), C.byref(nb)) == 3
+    assert b"225 taps (at most 223)" in lib.eoe_last_error()
+    # the filter refuses it before touching the GPU
+    assert lib.eoe_msm_filter(3, 16, 32, None, 2, 1, 226, 226, 224, None, 64, 1 << 30, None) == 3
+    assert b"225 taps (at most 223)" in lib.eoe_last_error()
 
 
 def test_msm_entry_points_validate_arguments():

@@ -9,12 +9,33 @@ import torch
 pytestmark = pytest.mark.gpu
 
 K_NOISE = 3.0
-MAGNITUDES = (0, 1, 2, 4, 8, 16, 32)
+MAGNITUDES = (0, 1, 2, 4, 8, 16, 32)                       # multiscale_cifar.py
+IMAGENET_MAGNITUDES = (0, 1, 2, 4, 8, 16, 32, 64, 128, 256)  # multiscale_imagenet.py
+# 224^2: the ImageNet list, plus 100 (r = 24: the far end of the branches that 64 enters, lpf direct / hpf complement)
+MAGNITUDES_224 = IMAGENET_MAGNITUDES + (100,)
 
 
 def _images(shape, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.rand(shape, generator=g, dtype=torch.float32)
+
+
+def test_224_magnitudes_reach_every_rank_limited_branch():
+    """G = c I + s U U^H at 224^2: every (op, kept set / complement) pair runs with r > 0 under MAGNITUDES_224, so the GEMM chain
+    is exercised with the c s terms both zero and non-zero for both ops"""
+    from eoe_amd.msm import host_operator
+    seen = {}
+    for op in ("lpf", "hpf"):
+        for mag in MAGNITUDES_224:
+            if mag <= 0:
+                continue
+            u, (c, s) = host_operator(op, 224, mag, True)
+            assert (c, s) in ((0.0, 1.0), (1.0, -1.0))
+            if u.shape[1] > 0:
+                seen.setdefault((op, c), []).append((mag, u.shape[1]))
+    print("224^2 branches with r > 0 (op, c): [(magnitude, r)]:", seen)
+    assert set(seen) == {("lpf", 0.0), ("lpf", 1.0), ("hpf", 0.0), ("hpf", 1.0)}, seen
+    assert (64, 96) in seen[("lpf", 0.0)] and (64, 96) in seen[("hpf", 1.0)]
 
 
 @pytest.mark.parametrize("shape", [(256, 3, 32, 32), (8, 1, 28, 28), (16, 3, 224, 224)])
@@ -25,7 +46,7 @@ def test_fft_filters_match_fp64(shape, op):
     xd = x.cuda()
     x_before = xd.clone()
     x64 = x.double().numpy()
-    for mag in MAGNITUDES:
+    for mag in (MAGNITUDES_224 if shape[-1] == 224 else MAGNITUDES):
         got = msm_filter(xd, op, mag).cpu().numpy()
         if mag == 0:
             assert np.array_equal(got.view(np.uint32), x.numpy().view(np.uint32)), "magnitude 0 is a bit copy"
@@ -35,12 +56,15 @@ def test_fft_filters_match_fp64(shape, op):
         nan = np.isnan(want)
         assert np.array_equal(np.isnan(got), nan) and np.array_equal(np.isnan(ref32), nan), (op, mag)
         if nan.all():
+            print(f"{op} {shape} magnitude {mag}: all NaN, as the reference")
             continue
         # a fully zeroed spectrum is per image: rows are either all NaN or all finite
         assert not (nan.reshape(shape[0], -1).any(1) & ~nan.reshape(shape[0], -1).all(1)).any()
         dist = np.abs(ref32[~nan] - want[~nan]).max()
         err = np.abs(got[~nan].astype(np.float64) - want[~nan]).max()
-        assert err <= max(K_NOISE * dist, 1e-6), (op, mag, err, dist)
+        bar = max(K_NOISE * dist, 1e-6)
+        print(f"{op} {shape} magnitude {mag}: max err {err:.3e}, dist32 {dist:.3e}, bar {bar:.3e}")
+        assert err <= bar, (op, mag, err, dist)
     assert torch.equal(xd, x_before), "the input is not modified"
 
 
@@ -54,30 +78,60 @@ def test_fully_zeroed_spectrum_gives_nan_rows():
         assert torch.isnan(msm_filter(x, op, mag)).all(), (op, mag)
 
 
-@pytest.mark.parametrize("shape", [(64, 3, 32, 32), (8, 1, 28, 28), (6, 3, 224, 224)])
-@pytest.mark.parametrize("op", ["lpf", "hpf", "blur"])
-def test_row_selection_copies_unselected_rows_bitwise(shape, op):
+def _check_row_selection(shape, op, mag):
     from eoe_amd.msm import msm_filter
     x = _images(shape, 7).cuda()
     x_before = x.clone()
     rows = torch.arange(shape[0], device="cuda") % 3 == 1
-    full = msm_filter(x, op, 4)
-    part = msm_filter(x, op, 4, rows)
+    full = msm_filter(x, op, mag)
+    part = msm_filter(x, op, mag, rows)
     assert torch.equal(x, x_before)
     assert torch.equal(part[~rows].view(torch.int32), x[~rows].view(torch.int32))
     assert torch.equal(part[rows].view(torch.int32), full[rows].view(torch.int32))
 
 
+@pytest.mark.parametrize("shape", [(64, 3, 32, 32), (8, 1, 28, 28), (6, 3, 224, 224)])
+@pytest.mark.parametrize("op", ["lpf", "hpf", "blur"])
+def test_row_selection_copies_unselected_rows_bitwise(shape, op):
+    _check_row_selection(shape, op, 4)
+
+
+@pytest.mark.parametrize("op", ["lpf", "hpf", "blur"])
+def test_row_selection_at_224_magnitude_64(op):
+    """magnitude 64 at 224^2: lpf on the kept set and hpf on the complement (r = 96), blur with 65 taps"""
+    _check_row_selection((6, 3, 224, 224), op, 64)
+
+
 @pytest.mark.parametrize("shape", [(32, 3, 32, 32), (8, 1, 28, 28), (4, 3, 224, 224)])
 def test_blur_matches_restatement(shape):
-    from eoe_amd.msm import blur_np, msm_filter
+    from eoe_amd.msm import blur_np, blur_taps_k, msm_filter
     x = _images(shape, 5)
     xd = x.cuda()
-    for sigma in (1, 2, 4, 8, 16, 32):
+    for sigma in (1, 2, 4, 8, 16, 32, 64, 128, 256):     # k up to 223 at 224^2; capped at 31 / 27 at 32^2 / 28^2
         got = msm_filter(xd, "blur", sigma).cpu().numpy()
         want = blur_np(x.numpy(), sigma)
-        assert np.abs(got - want).max() <= 1e-5, (shape, sigma)
+        err = np.abs(got - want).max()
+        print(f"blur {shape} sigma {sigma} k {blur_taps_k(sigma, shape[-1])}: max err {err:.3e}")
+        assert err <= 1e-5, (shape, sigma)
     assert torch.equal(msm_filter(xd, "blur", 0), xd)
+
+
+@pytest.mark.parametrize("op", ["lpf", "hpf", "blur"])
+def test_apply_msms_test_anomalous_at_imagenet_magnitudes(op):
+    """`<op>+test_anomalous` on a labelled 224^2 test batch at the ImageNet driver's 64 and 256 (lpf / hpf 256: NaN rows, as the
+    reference): the anomalous rows are msm_filter of those rows bit for bit, the nominal rows bit copies"""
+    from eoe_amd.msm import MSM, apply_msms, msm_filter
+    x = _images((8, 3, 224, 224), 21).cuda()
+    x_before = x.clone()
+    lbls = torch.tensor([0, 1, 1, 0, 1, 0, 0, 1])
+    anom = (lbls != 0).cuda()
+    for mag in (64, 256):
+        out = apply_msms(x, lbls, [MSM.load(f"{op}+test_anomalous--M{mag}")], "test", 0)
+        assert out is not x
+        want = msm_filter(x[anom], op, mag)
+        assert torch.equal(out[anom].view(torch.int32), want.view(torch.int32)), (op, mag)
+        assert torch.equal(out[~anom].view(torch.int32), x[~anom].view(torch.int32)), (op, mag)
+    assert torch.equal(x, x_before)
 
 
 # --------------------------------------------------------------------------------------------------------------- trainer

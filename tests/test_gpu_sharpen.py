@@ -48,7 +48,9 @@ def test_sharpen_u8_general_radius_and_threshold(shape):
     from eoe_amd.msm import sharpen_u8, unsharp_np
     x = _u8(shape, shape[0] + shape[1])
     xd = x.cuda()
-    for percent, radius, threshold in ((400, 2.0, 3), (150, 0.5, 0), (3200, 3.3, 10), (100, 10.0, 3), (250, 0.0, 3)):
+    # 6400-25600: the ImageNet driver's magnitudes 64, 128, 256 (d * percent up to 255 * 25600)
+    for percent, radius, threshold in ((400, 2.0, 3), (150, 0.5, 0), (3200, 3.3, 10), (100, 10.0, 3), (250, 0.0, 3), (6400, 2.0, 3),
+                                       (12800, 2.0, 3), (25600, 2.0, 3)):
         if shape[1] * shape[2] > 4096 and radius == 10.0:
             continue                          # the restatement is slow on wide windows of big planes; 3x3 / 5x7 / 28^2 cover it
         got = sharpen_u8(xd, percent, radius=radius, threshold=threshold).cpu().numpy()
@@ -63,7 +65,7 @@ def test_msm_sharpen_on_the_tensor_grid_equals_tensor_of_pillow(shape):
     u8 = _u8((n, h, w, c), 3 + h)
     x = u8.permute(0, 3, 1, 2).float().div(255)                         # ToTensor's bits
     xd = x.cuda()
-    for mag in (1, 4, 32):
+    for mag in (1, 4, 32, 64, 128, 256):
         got = msm_sharpen(xd, mag).cpu()
         want = torch.from_numpy(unsharp_np(u8.numpy(), sharpen_percent(mag))).permute(0, 3, 1, 2).float().div(255)
         assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (shape, mag)
