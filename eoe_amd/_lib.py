@@ -17,6 +17,7 @@ EOE_F16, EOE_BF16, EOE_F32 = 1, 2, 3
 EOE_RESIZE_BILINEAR, EOE_RESIZE_BICUBIC = 2, 3
 EOE_MSM_LPF, EOE_MSM_HPF, EOE_MSM_BLUR = 1, 2, 3
 EOE_MSM_FORM_NONE, EOE_MSM_FORM_DENSE, EOE_MSM_FORM_RANK = 0, 1, 2
+EOE_GCN_L1, EOE_GCN_L2 = 1, 2
 EOE_COMM_I64, EOE_COMM_ID_BYTES, EOE_COMM_ALGO_RING, EOE_COMM_ALGO_RS_AG = 8, 128, 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD = 0, 1, 2, 3
 ADAM_CHUNK, ADAM_GROUPS = 8192, 4
@@ -234,6 +235,8 @@ SIGNATURES = {
     "eoe_msm_sharpen_u8": [_vp, _vp, _vp] + [C.c_int] * 4 + [_f32, C.c_int, C.c_int, _vp],
     "eoe_msm_sharpen_f32": [_vp, _vp, _vp] + [C.c_int] * 4 + [_f32, C.c_int, C.c_int, _vp],
     "eoe_crop_flip_u8": [_vp, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_set_moments_u8": [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp],
+    "eoe_gcn_normalize": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
     "eoe_comm_destroy": [_vp],

@@ -235,6 +235,13 @@ class ResidentImageSource:
     draws (index, crop origin, flip) per sample.  Batches come out already normalised, so `.normalize` is None (the trainer
     then installs no second Normalize).
 
+    `normalize` (optional): one of the reference's transform strings ('normalize' / 'gcn-normalize' and their spellings,
+    eoe_amd.normalize.NORM_MODES) instead of ready `mean` / `std`: the statistics are fitted as the reference fits them
+    (`bases.py:293-372`) over the resident normal set after `resize`, restricted to `normal_index`, unless `ds_statistics` (the
+    dict of a snapshot) is given, which wins (`bases.py:326-329`).  `.ds_statistics` then holds the dict.  'normalize' feeds the
+    `mean` / `std` path; under 'gcn-normalize' batches leave in the [0, 1] scale and `.normalize` is a
+    `GcnNormalize(shift, range, 'l1')` that the trainer runs on the step batch.
+
     `normal_index` (optional): the rows of `normal_u8` that ARE the normal training set -- the reference's `Subset` over the
     samples of the normal classes (`bases.py:169-203`); batches report those rows' indices in the full set, as the reference's
     datasets do (`cifar.py:106-121`), and OE indices are offset by the length of the FULL normal set (`bases.py:596`)."""
@@ -243,7 +250,7 @@ class ResidentImageSource:
 
     def __init__(self, normal_u8, oe_u8, test_u8, test_labels, crop, padding=0, mean=None, std=None, flip_first=True,
                  noise_std=0.001, seed=0, device="cuda", resize=None, test_resize=None, color_jitter=None, interpolation="bilinear",
-                 normal_index=None):
+                 normal_index=None, normalize=None, ds_statistics=None):
         """resize / test_resize: `transforms.Resize` argument applied once to the resident train / test sets (None: as given);
         color_jitter: (brightness, contrast, saturation, hue) of `transforms.ColorJitter`, drawn per sample per step"""
         dev = torch.device(device)
@@ -259,13 +266,38 @@ class ResidentImageSource:
         self.normalize = None
         self.ds_statistics = None
         self.normal_index = None if normal_index is None else torch.as_tensor(normal_index, dtype=torch.int64).clone()
+        self._gcn = None
+        if normalize is not None:
+            self._resolve_normalize(normalize, ds_statistics)
+        elif ds_statistics is not None:
+            raise ValueError("ds_statistics needs the normalisation mode they belong to (normalize=...)")
         self._g = torch.Generator().manual_seed(seed)
         self._step = 0
+
+    def _resolve_normalize(self, normalize, ds_statistics):
+        """turn the transform string into numbers, once per task (`bases.py:293-372`).  Under data parallelism every rank does
+        this on its own copy of the set: the fit works on exact integer sums, so all ranks get the same bits without a collective."""
+        from . import normalize as _norm
+        if self.mean is not None or self.std is not None:
+            raise ValueError("normalize= fits the statistics itself; it cannot be combined with mean= / std=")
+        mode = _norm.norm_mode(normalize)
+        if ds_statistics is not None:
+            stats = _norm.check_ds_statistics(ds_statistics, mode)
+        else:
+            stats = _norm.fit_statistics(self.normal, self.normal_index, normalize)
+        self.ds_statistics = stats
+        if mode == _norm.STD_NORM:
+            self.mean, self.std = list(stats["mean"]), list(stats["std"])
+        else:
+            self._gcn = _norm.GcnNormalize.from_statistics(stats, "l1")
+            self.normalize = self._gcn
 
     def defer_normalize(self, on: bool = True):
         """leave Normalize out of the batches and report (mean, std) as `.normalize` for the encoder's fused normalise: the
         multi-scale modes filter in the [0, 1] pixel scale, before Normalize (training/ad_trainer.py:413-425)"""
         self._defer = bool(on)
+        if self._gcn is not None:                        # GCN mode: batches are in the [0, 1] scale anyway, the operator stays
+            return
         self.normalize = (self.mean, self.std) if on and self.mean is not None else None
 
     def _norm_args(self):
@@ -388,20 +420,35 @@ class LabelledImageSet:
     The images are uploaded once; a task is an index list over them (`ResidentImageSource(normal_index=...)`), so iterating 30
     classes x 2 seeds does not copy the set 60 times."""
 
-    def __init__(self, train_u8, train_classes, test_u8, test_classes, oe_u8, classes, crop, device="cuda", **source_kw):
+    def __init__(self, train_u8, train_classes, test_u8, test_classes, oe_u8, classes, crop, device="cuda", normalize=None,
+                 **source_kw):
+        """normalize: one of the reference's transform strings ('normalize', 'gcn-normalize', ...): every task then gets the
+        statistics of ITS normal classes (`bases.py:293-372`), fitted once per class set and kept (the reference keeps them in
+        `stats_cache.json`, `bases.py:374-410`): thirty classes x two seeds fit thirty times"""
         dev = torch.device(device)
         self.train, self.test, self.oe = (t.to(dev).contiguous() for t in (train_u8, test_u8, oe_u8))
         self.train_classes = torch.as_tensor(train_classes, dtype=torch.int64).clone()
         self.test_classes = torch.as_tensor(test_classes, dtype=torch.int64).clone()
         self.classes = list(classes)
         self.crop, self.source_kw, self.device = crop, dict(source_kw), dev
+        self.normalize, self._stats = normalize, {}
 
     def no_classes(self) -> int:
         return len(self.classes)
 
-    def source(self, normal_classes, seed: int = 0) -> ResidentImageSource:
+    def source(self, normal_classes, seed: int = 0, ds_statistics=None) -> ResidentImageSource:
+        """ds_statistics: the dict of a snapshot to score with (wins over fitting, and is not kept for later tasks); it is used
+        only by a set built with `normalize=`: one built with ready `mean=` / `std=` keeps those, whatever a snapshot carries"""
+        key = tuple(sorted(int(c) for c in normal_classes))
+        given = ds_statistics if ds_statistics is not None else self._stats.get(key)
+        kw = dict(self.source_kw)
+        if self.normalize is not None:
+            kw.update(normalize=self.normalize, ds_statistics=given)
+        # without a mode the set was built with ready mean= / std= (or none): a snapshot's statistics are not looked at, as before
         src = ResidentImageSource(self.train, self.oe, self.test, ad_targets(self.test_classes, normal_classes), self.crop,
                                   seed=seed, device=self.device, normal_index=normal_subset(self.train_classes, normal_classes),
-                                  **self.source_kw)
+                                  **kw)
+        if self.normalize is not None and ds_statistics is None:
+            self._stats.setdefault(key, src.ds_statistics)
         src.normal_classes = tuple(int(c) for c in normal_classes)
         return src

@@ -15,7 +15,14 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
   * multi-scale modes (`msms`, eoe_amd.msm): lpf / hpf / blur run as HIP kernels on the device batch after `.to(device)`
     and before the encoder's fused Normalize (:413-425 train, :501-505 test); so does `sharpen` (Pillow's UnsharpMask, a HIP
     kernel on the [0, 1] batch quantised to uint8; GPU devices only), unless the source applies it to its uint8 images before
-    ToTensor and the noise as the reference does (ResidentImageSource.pre_tensor_msms).
+    ToTensor and the noise as the reference does (ResidentImageSource.pre_tensor_msms);
+  * a source in 'gcn-normalize' mode reports a `GcnNormalize` as `.normalize`: global contrast normalisation is per sample, not a
+    per-channel affine, so the encoder's fused normalise is switched off and one HIP launch (eoe_amd.normalize.gcn_normalize)
+    runs on the step batch after the multi-scale modes and before the encoder (:415-425), in training and in scoring;
+  * `run(load=[[path]], train=False)` loads the snapshot's weights into the model before scoring it, together with the
+    `ds_statistics` stored in the file.  The reference only takes the statistics from the file there and scores a freshly reset
+    model (:257-264), which makes "score this snapshot again" impossible without training; a module handed in through `load` is
+    scored as is, as in the reference.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -30,6 +37,7 @@ import torch
 from .. import ops, parallel
 from ..metrics import ROC, PRC, roc_auc, average_precision, auc_ap_device
 from ..msm import apply_msms, check_supported
+from ..normalize import GcnNormalize
 from ..optim import FusedAdam
 
 
@@ -123,6 +131,7 @@ class ADTrainer(ABC):
         self.msms = list(msms or ())
         check_supported(self.msms, self.device)          # sharpen on a CPU device raises NotImplementedError
         self._step_msms = self.msms                         # the train MSMs left to the step batch (_msm_source)
+        self._gcn = None                                    # the task's GcnNormalize, if its source is in that mode (_normalize_hook)
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -136,7 +145,7 @@ class ADTrainer(ABC):
             return [c % n for c in range(cur_class, n // 2 + cur_class)]
         raise NotImplementedError(f"AD mode {self.ad_mode} unknown. Known modes are {ADTrainer.AD_MODES}.")
 
-    def _dataset(self, c: int, seed: int):
+    def _dataset(self, c: int, seed: int, ds_statistics: Optional[dict] = None):
         """the task of one (class, seed) run.  The reference builds it with `load_dataset(dsstr, datapath,
         self.get_nominal_classes(c), 0, ...)` unless `trainer.ds` was pre-set (ad_trainer.py:248-253): here a pre-built
         step-batch source is used as is, a labelled image set (`.source(normal_classes, seed)`) is asked for the task of the
@@ -144,6 +153,8 @@ class ADTrainer(ABC):
         if self.ds is not None:
             return self.ds
         if hasattr(self.dsstr, "source"):
+            if ds_statistics is not None:            # a snapshot's statistics win over fitting them again (bases.py:326-329)
+                return self.dsstr.source(self.get_nominal_classes(c), seed, ds_statistics=ds_statistics)
             return self.dsstr.source(self.get_nominal_classes(c), seed)
         if callable(self.dsstr):
             return self.dsstr(c, seed)
@@ -166,18 +177,32 @@ class ADTrainer(ABC):
     def _train_with_retries(self, c: int, cstr: str, seed: int, preset, train: bool):
         """NaN scores abort a run (`NanGradientsError`); the reference then starts over on a freshly built dataset with fresh
         weights.  Returns (model, training ROC, dataset); the model is None only if the reference would return None"""
-        ds = self._dataset(c, seed)
+        # a snapshot to load brings the statistics its model was trained with (ad_trainer.py:248-252)
+        # (the file is read once here and kept for this run: `load` below takes the weights from the same read)
+        stats = None
+        if isinstance(preset, str):
+            self._snapshot_read = (preset, self.unify_snapshot_style(torch.load(preset, map_location="cpu")))
+            stats = self.load_ds_statistics(preset)
+        try:
+            return self._train_attempts(c, cstr, seed, preset, train, stats)
+        finally:
+            self._snapshot_read = None
+
+    def _train_attempts(self, c: int, cstr: str, seed: int, preset, train: bool, stats):
+        ds = self._dataset(c, seed, stats)
         model = roc = None
         for attempt in range(self.NAN_ATTEMPTS):
             model = self._fresh_model(preset)
             try:
                 if train:
                     model, roc = self.train_cls(model, ds, c, cstr, seed, preset)
+                elif isinstance(preset, str):
+                    self.load(preset, model)             # score a snapshot file: its weights with its statistics
                 return model, roc, ds
             except NanGradientsError:
                 self.logger.warning(f'NaN scores while training class {c} "{cstr}", seed {seed} (failure {attempt + 1} of '
                                     f'{self.NAN_ATTEMPTS}); retrying with fresh weights and data.')
-                ds = self._dataset(c, seed)
+                ds = self._dataset(c, seed, stats)
                 if attempt + 1 == self.NAN_GIVE_UP_AT:
                     model = roc = None
         return model, roc, ds
@@ -247,6 +272,12 @@ class ADTrainer(ABC):
         encoders that do not"""
         norm = getattr(ds, "normalize", None)
         enc = getattr(model, "feature_model", model)
+        self._gcn = norm if isinstance(norm, GcnNormalize) else None
+        if self._gcn is not None:
+            # per-sample statistics: not expressible as the encoder's per-channel (mean, std); the step loop runs the operator
+            if hasattr(enc, "set_normalize"):
+                enc.set_normalize(None, None)
+            return None
         if hasattr(enc, "set_normalize"):
             enc.set_normalize(*(norm if norm is not None else (None, None)))
             return None
@@ -351,6 +382,8 @@ class ADTrainer(ABC):
                     lbls = lbls.to(self.device, non_blocking=True)                                      # :412
                     if self.msms:                                                                       # :413-425
                         imgs = apply_msms(imgs, lbls, self._step_msms, "train", nominal)
+                    if self._gcn is not None:                                                           # :415-425, after the MSMs
+                        imgs = self._gcn(imgs)                # a graphed step below gets the normalised batch
                     opt.zero_grad()                                                                     # :428
                     if self.graph_steps and world == 1 and graphed is None:
                         from ..graph import GraphedStep
@@ -424,6 +457,8 @@ class ADTrainer(ABC):
                 imgs, lbls = batch[0].to(self.device), batch[1]
                 if self.msms:                                                                           # :501-505
                     imgs = apply_msms(imgs, lbls, self.msms, "test", nominal)
+                if self._gcn is not None:
+                    imgs = self._gcn(imgs)
                 with torch.no_grad():
                     feats = model(imgs)
                 ep_scores.append(self.compute_anomaly_score(feats, center, inputs=imgs, nominal_label=nominal))
@@ -457,7 +492,7 @@ class ADTrainer(ABC):
         freeze its encoder does so here -- this is where the reference applies `freeze_parts` (:593-596)."""
         epoch = 0
         if path is not None:
-            snap = self.unify_snapshot_style(torch.load(path, map_location="cpu"))
+            snap = self._read_snapshot(path)
             encoder_weights = snap.get("feature_model")
             if encoder_weights is not None:
                 if not hasattr(model, "load_feature_model_weights"):
@@ -472,6 +507,19 @@ class ADTrainer(ABC):
         if hasattr(model, "freeze_parts"):
             model.freeze_parts()
         return epoch
+
+    def load_ds_statistics(self, path: str) -> Optional[dict]:
+        """the normalisation statistics a snapshot was trained with (`ad_trainer.py:600-603`); None for a file without any"""
+        if path is None:
+            return None
+        return self._read_snapshot(path).get("ds_statistics")
+
+    def _read_snapshot(self, path: str) -> dict:
+        """the unified snapshot dict of a file: the read `run` keeps for the (class, seed) pair it is working on, else a fresh one"""
+        kept = getattr(self, "_snapshot_read", None)
+        if kept is not None and kept[0] == path:
+            return kept[1]
+        return self.unify_snapshot_style(torch.load(path, map_location="cpu"))
 
     def unify_snapshot_style(self, snapshot: dict) -> dict:
         """map both accepted file layouts onto one dict (`ad_trainer.py:608-615`)"""

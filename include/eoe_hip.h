@@ -599,6 +599,30 @@ int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int Ws, const in
                      int flip_first, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Per-task input normalisation: the reference's 'normalize' / 'gcn-normalize' transform strings (datasets/bases.py:293-372).
+ *   eoe_set_moments_u8  the statistics pass over a resident uint8 NHWC set [n_src, H, W, C] (C = 1 or 3), one launch.  index:
+ *                       n_index int64 rows of the set on the DEVICE (NULL = rows 0 .. n_index - 1).  All outputs are exact
+ *                       integers (int64, DEVICE): chan_sums [n_index][C][2] = per channel (sum v, sum v^2); img_stats
+ *                       [n_index][3] = per image over all channels (min v, max v, sum |N v - S|) with N = C*H*W and S = sum v
+ *                       over the image, so the image's mean absolute deviation in the [0, 1] scale is that sum / (255 N^2).
+ *                       A row outside [0, n_src) reads nothing and gets -1 in all its outputs.  Integer sums: independent of
+ *                       the reduction order, bitwise repeatable.  The host turns them into the reference's RunningStats
+ *                       recurrence / GCN extremes (eoe_amd/normalize.py).
+ *   eoe_gcn_normalize   global contrast normalisation (utils/transformations.py:326-349) and the per-channel Normalize that
+ *                       follows it, fp32 NCHW [n, C, H, W] (C = 1 or 3): y = ((x - mean_i) / scale_i - shift[c]) / range[c],
+ *                       mean_i over the N = C*H*W features of sample i, scale_i = mean |x - mean_i| (EOE_GCN_L1) or
+ *                       sqrt(sum (x - mean_i)^2) / N (EOE_GCN_L2).  shift / range: C floats each on the DEVICE, both or
+ *                       neither (NULL, NULL = GCN alone).  y == x (in place) is allowed and gives the same bits; partial
+ *                       overlap is not.  No epsilon: a constant sample gives non-finite values, as in the reference.  One
+ *                       launch, fixed summation order (fp64 sums), no atomics.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { EOE_GCN_L1 = 1, EOE_GCN_L2 = 2 };
+int eoe_set_moments_u8(const uint8_t* src, int64_t n_src, int H, int W, int C, const int64_t* index, int64_t n_index,
+                       int64_t* chan_sums, int64_t* img_stats, void* stream);
+int eoe_gcn_normalize(const float* x, float* y, int n, int C, int H, int W, int scale, const float* shift, const float* range,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Data-parallel exchange (new -- the reference is single-device, main/__init__.py:110-114): gradient
  * SUM all-reduce and score / label all-gather over RCCL on xGMI, one process per GPU.  RCCL is bound at run time (the librccl
  * already in the process, else the system one); without it these return EOE_ERR_UNSUPPORTED and nothing else is affected.
