@@ -237,6 +237,9 @@ SIGNATURES = {
     "eoe_crop_flip_u8": [_vp, _i64, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_set_moments_u8": [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp],
     "eoe_gcn_normalize": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
+    "eoe_pool_sqdist_workspace": [_i64, C.c_int, C.c_int, C.POINTER(_sz)],
+    "eoe_pool_sqdist_u8": [_vp, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp],
+    "eoe_pool_rank": [_vp, C.c_int, C.c_int, _vp, _vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
     "eoe_comm_destroy": [_vp],

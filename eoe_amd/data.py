@@ -273,6 +273,25 @@ class ResidentImageSource:
             raise ValueError("ds_statistics needs the normalisation mode they belong to (normalize=...)")
         self._g = torch.Generator().manual_seed(seed)
         self._step = 0
+        self.oe_subset = None
+
+    def set_oe_subset(self, indices=None):
+        """restrict outlier exposure to the listed rows of the resident OE set (None: the full set again): the OE half of every
+        step batch is drawn only from them.  This is the reference's `oe_limit_samples` / the evolve experiment's
+        `oe.train_set.indices = [...]` (`bases.py:196-201`, `evolve/__init__.py:71-77`): a `Subset` over the OE data.  As there,
+        the list is tiled when it is shorter than the normal set (`bases.py:580-584`), the with-replacement rule looks at the
+        length of the SUBSET (`bases.py:561`), and a batch reports for an OE sample its row in the FULL OE set (the wrapped
+        dataset returns its own index, `cifar.py:106-121`: a `Subset` does not renumber) plus the length of the full normal set
+        (`bases.py:596`).  Rows may repeat; order is kept."""
+        if indices is None:
+            self.oe_subset = None
+            return
+        idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int64)
+        if idx.numel() == 0:
+            raise ValueError("an OE subset needs at least one row (None restores the full set)")
+        if int(idx.min()) < 0 or int(idx.max()) >= self.oe.shape[0]:
+            raise IndexError(f"OE subset names rows outside the resident OE set of {self.oe.shape[0]} images")
+        self.oe_subset = idx
 
     def _resolve_normalize(self, normalize, ds_statistics):
         """turn the transform string into numbers, once per task (`bases.py:293-372`).  Under data parallelism every rank does
@@ -336,9 +355,10 @@ class ResidentImageSource:
 
     def _epoch(self, batch_size):
         subset = self.normal_index if self.normal_index is not None else torch.arange(self.normal.shape[0])
-        n, n_full, m = len(subset), self.normal.shape[0], self.oe.shape[0]
+        oe_rows = self.oe_subset if self.oe_subset is not None else torch.arange(self.oe.shape[0])
+        n, n_full, m = len(subset), self.normal.shape[0], len(oe_rows)
         perm = subset[torch.randperm(n, generator=self._g)]
-        oe_idx = tile_oe_indices(torch.arange(m), n)
+        oe_idx = tile_oe_indices(oe_rows, n)
         if m >= 10000:                                   # bases.py:561: OE sets of >= 10 000 samples are drawn with replacement
             oe_order = oe_idx[torch.randint(len(oe_idx), (len(oe_idx),), generator=self._g)]
         else:
@@ -436,9 +456,10 @@ class LabelledImageSet:
     def no_classes(self) -> int:
         return len(self.classes)
 
-    def source(self, normal_classes, seed: int = 0, ds_statistics=None) -> ResidentImageSource:
+    def source(self, normal_classes, seed: int = 0, ds_statistics=None, oe_subset=None) -> ResidentImageSource:
         """ds_statistics: the dict of a snapshot to score with (wins over fitting, and is not kept for later tasks); it is used
-        only by a set built with `normalize=`: one built with ready `mean=` / `std=` keeps those, whatever a snapshot carries"""
+        only by a set built with `normalize=`: one built with ready `mean=` / `std=` keeps those, whatever a snapshot carries.
+        oe_subset: rows of the OE set to restrict outlier exposure to (`ResidentImageSource.set_oe_subset`)"""
         key = tuple(sorted(int(c) for c in normal_classes))
         given = ds_statistics if ds_statistics is not None else self._stats.get(key)
         kw = dict(self.source_kw)
@@ -451,4 +472,6 @@ class LabelledImageSet:
         if self.normalize is not None and ds_statistics is None:
             self._stats.setdefault(key, src.ds_statistics)
         src.normal_classes = tuple(int(c) for c in normal_classes)
+        if oe_subset is not None:
+            src.set_oe_subset(oe_subset)
         return src

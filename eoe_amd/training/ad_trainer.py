@@ -128,6 +128,8 @@ class ADTrainer(ABC):
         # "auto" = on for a BatchNorm encoder trained with lr >= 1e-3 (every BatchNorm runner of the reference: train_cifar.py:17,
         # train_imagenet.py:16), True / False = forced.  The ViT has no BatchNorm and meets the bar in its 16-bit mode.
         self.exact_bn = exact_bn
+        # int k < inf: k random OE samples per task; a list: exactly those rows of the OE set (bases.py:196-201); inf: all (_limit_oe)
+        self.oe_limit_samples = oe_limit_samples
         self.msms = list(msms or ())
         check_supported(self.msms, self.device)          # sharpen on a CPU device raises NotImplementedError
         self._step_msms = self.msms                         # the train MSMs left to the step batch (_msm_source)
@@ -145,8 +147,34 @@ class ADTrainer(ABC):
             return [c % n for c in range(cur_class, n // 2 + cur_class)]
         raise NotImplementedError(f"AD mode {self.ad_mode} unknown. Known modes are {ADTrainer.AD_MODES}.")
 
+    def _limit_oe(self, ds):
+        """`oe_limit_samples` as the reference's `create_subset` applies it to the OE data when a task's dataset is made
+        (`bases.py:196-201`): an int k < inf keeps `sorted(np.random.choice(n, min(k, n), False))`, a list exactly its rows.  The
+        default (inf) does not touch the source.  A pre-built `trainer.ds` is restricted the same way each time a run asks for it
+        (the evolve experiment sets the list per individual, `evolve/__init__.py:70-73`)."""
+        limit = self.oe_limit_samples
+        if isinstance(limit, (int, float)):
+            if not limit < np.inf:
+                return ds
+            if limit < 1:
+                raise ValueError(f"oe_limit_samples must be at least 1, not {limit}")
+        if not hasattr(ds, "set_oe_subset"):
+            raise NotImplementedError(f"oe_limit_samples needs a source whose OE set can be restricted (set_oe_subset); "
+                                      f"{type(ds).__name__} has none")
+        if isinstance(limit, (int, float)):
+            n = int(ds.oe.shape[0])
+            rows = sorted(np.random.choice(n, min(int(limit), n), False))
+        else:
+            rows = list(limit)
+        ds.set_oe_subset([int(r) for r in rows])
+        return ds
+
     def _dataset(self, c: int, seed: int, ds_statistics: Optional[dict] = None):
-        """the task of one (class, seed) run.  The reference builds it with `load_dataset(dsstr, datapath,
+        """the task of one (class, seed) run (`_task_source`), its outlier exposure limited to `oe_limit_samples`"""
+        return self._limit_oe(self._task_source(c, seed, ds_statistics))
+
+    def _task_source(self, c: int, seed: int, ds_statistics: Optional[dict] = None):
+        """The reference builds the task with `load_dataset(dsstr, datapath,
         self.get_nominal_classes(c), 0, ...)` unless `trainer.ds` was pre-set (ad_trainer.py:248-253): here a pre-built
         step-batch source is used as is, a labelled image set (`.source(normal_classes, seed)`) is asked for the task of the
         current AD mode, and a callable (cls, seed) -> source decides for itself."""

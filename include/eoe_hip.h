@@ -623,6 +623,27 @@ int eoe_gcn_normalize(const float* x, float* y, int n, int C, int H, int W, int 
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Candidate search of the evolutionary OE-sample experiment (evolve/__init__.py:100-157: the squared distances of a pool of
+ * candidate images to the parent image(s) and their sorted order), on a resident uint8 image set [n_set][D] (D = H*W*C bytes per
+ * image, any layout: both sides of a difference are read the same way).
+ *   eoe_pool_sqdist_u8   out[k][p] = sum_e (set[query_idx[k]][e] - set[cand_idx[p]][e])^2, exact int64 [K][P] on the DEVICE.
+ *                        query_idx / cand_idx are HOST arrays (K <= 1024, P <= 2^20 rows; repeats allowed, a query may be a
+ *                        candidate): they are checked against n_set before anything is launched (EOE_ERR_ARG, nothing is read)
+ *                        and copied into the workspace on `stream`, so they must stay valid until the stream has passed the call.
+ *                        Every candidate is read from memory once and compared with all K queries.  D is split over workgroups
+ *                        (chunks of 1 KiB .. 64 KiB, about 1 024 workgroups); a chunk sums in 32 bits, chunks are added in 64 bits
+ *                        by a second small launch (no atomics; integer sums, so bitwise repeatable either way).  D % 16 != 0
+ *                        takes a byte-wise path.  workspace: eoe_pool_sqdist_workspace(D, K, P) bytes, 16-byte aligned.
+ *   eoe_pool_rank        order[k][.] = the stable ascending order of dist[k][.] as positions 0 .. P-1 (equal distances keep list
+ *                        order: the `arg` of torch's stable sort), int32 [K][P], DEVICE; dist int64 [K][P].  One launch, rank by
+ *                        counting in LDS.  P <= 1024, larger P is EOE_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------------- */
+int eoe_pool_sqdist_workspace(int64_t D, int K, int P, size_t* bytes_out);
+int eoe_pool_sqdist_u8(const uint8_t* set, int64_t n_set, int64_t D, const int32_t* query_idx, int K, const int32_t* cand_idx, int P,
+                       int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+int eoe_pool_rank(const int64_t* dist, int K, int P, int32_t* order, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Data-parallel exchange (new -- the reference is single-device, main/__init__.py:110-114): gradient
  * SUM all-reduce and score / label all-gather over RCCL on xGMI, one process per GPU.  RCCL is bound at run time (the librccl
  * already in the process, else the system one); without it these return EOE_ERR_UNSUPPORTED and nothing else is affected.
