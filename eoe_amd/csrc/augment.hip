@@ -64,20 +64,126 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
 
 }  // namespace
 
-extern "C" int eoe_augment_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, const float* mean,
-                                 const float* stdv, float* out, int n, int Ho, int Wo, int flip_first, float noise_std,
-                                 uint64_t seed, void* stream) {
+// ---- one-channel form (the 28 x 28 tasks, main/train_fmnist.py:31-38, main/train_mnist.py): with one byte per pixel a thread per
+// pixel wastes the gather, so a thread takes 4 adjacent output pixels of a row.  Along a row the source column is s0 + dir * x
+// (dir = -1 when flipped), so where the 4 columns lie inside the image they are 4 consecutive bytes: one load.
+namespace {
+
+// v[k] = the source byte of output pixel (y, x0 + k) of batch slot b, k = 0..3; 0 in the zero padding, for x0 + k >= Wo (never
+// stored) and for a slot whose image index lies outside the set
+__device__ __forceinline__ void gather4_c1(const uint8_t* __restrict__ src, long long n_src, const int32_t* __restrict__ params, int b,
+                                           int y, int x0, int Hs, int Ws, int Wo, int flip_first, int v[4]) {
+    const int idx = params[b * 4 + 0], top = params[b * 4 + 1], left = params[b * 4 + 2], flip = params[b * 4 + 3];
+    v[0] = v[1] = v[2] = v[3] = 0;
+    const int sy = top + y;
+    if (sy < 0 || sy >= Hs || idx < 0 || (long long)idx >= n_src) return;
+    int s0, dir;                                                         // source column of output column x: s0 + dir * x
+    if (!flip) { s0 = left; dir = 1; }
+    else if (flip_first) { s0 = Ws - 1 - left; dir = -1; }               // flip the source, then crop
+    else { s0 = left + Wo - 1; dir = -1; }                               // crop, then flip the crop
+    const uint8_t* row = src + ((size_t)idx * Hs + sy) * Ws;
+    const int sa = s0 + dir * x0, sb = s0 + dir * (x0 + 3);              // first and last of the 4 source columns
+    const int lo = dir > 0 ? sa : sb;
+    if (x0 + 3 < Wo && lo >= 0 && lo + 3 < Ws) {
+        unsigned w;
+        __builtin_memcpy(&w, row + lo, 4);                               // any alignment: left is arbitrary
+        if (dir < 0) w = __builtin_bswap32(w);
+        v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                        // a padded border, or the ragged end of a row
+        const int sx = sa + dir * k;
+        if (x0 + k < Wo && sx >= 0 && sx < Ws) v[k] = row[sx];
+    }
+}
+
+// thread per (slot, row, quad of 4 columns); VEC: Wo % 4 == 0 and `out` 16-byte aligned, the quad leaves as one float4
+template <bool VEC>
+__global__ __launch_bounds__(256) void augment_c1_kernel(const uint8_t* __restrict__ src, long long n_src, const int32_t* __restrict__ params,
+                                                         const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                         float* __restrict__ out, int n, int Hs, int Ws, int Ho, int Wo,
+                                                         int flip_first, float noise_std, unsigned long long seed) {
+    const int Q = (Wo + 3) / 4;
+    const size_t total = (size_t)n * Ho * Q;
+    const float m = mean ? mean[0] : 0.f, s = mean ? stdv[0] : 1.f;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x0 = (int)(i % Q) * 4, y = (int)((i / Q) % Ho), b = (int)(i / ((size_t)Q * Ho));
+        int v[4];
+        gather4_c1(src, n_src, params, b, y, x0, Hs, Ws, Wo, flip_first, v);
+        float a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            a[k] = (float)v[k] / 255.0f;                                     // ToTensor
+            if (noise_std > 0.f) {                                           // the rule of augment_kernel with c = 0
+                const unsigned long long e = (unsigned long long)y * Wo + (x0 + k);
+                const unsigned long long z = splitmix64((seed << 40) + ((unsigned long long)b << 18) + e);
+                const float u1 = (float)((z >> 40) + 1ull) * (1.0f / 16777216.0f);          // (0, 1]
+                const float u2 = (float)((z >> 16) & 0xFFFFFFull) * (1.0f / 16777216.0f);   // [0, 1)
+                a[k] += noise_std * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+            }
+            if (mean) a[k] = (a[k] - m) / s;
+        }
+        float* o = out + ((size_t)b * Ho + y) * Wo + x0;
+        if (VEC) *reinterpret_cast<float4*>(o) = make_float4(a[0], a[1], a[2], a[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < Wo) o[k] = a[k];
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void crop_flip_c1_kernel(const uint8_t* __restrict__ src, long long n_src, const int32_t* __restrict__ params,
+                                                           uint8_t* __restrict__ out, int n, int Hs, int Ws, int Ho, int Wo, int flip_first) {
+    const int Q = (Wo + 3) / 4;
+    const size_t total = (size_t)n * Ho * Q;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x0 = (int)(i % Q) * 4, y = (int)((i / Q) % Ho), b = (int)(i / ((size_t)Q * Ho));
+        int v[4];
+        gather4_c1(src, n_src, params, b, y, x0, Hs, Ws, Wo, flip_first, v);
+        uint8_t* o = out + ((size_t)b * Ho + y) * Wo + x0;
+        if (VEC) *reinterpret_cast<unsigned*>(o) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < Wo) o[k] = (uint8_t)v[k];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int eoe_augment_batch_c(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, const float* mean,
+                                   const float* stdv, float* out, int n, int Ho, int Wo, int flip_first, float noise_std,
+                                   uint64_t seed, void* stream) {
+    EOE_CHECK_ARG(C == 1 || C == 3, "augment_batch: C must be 1 or 3, not %d", C);
     EOE_CHECK_ARG(src && params && out && n_src > 0 && n > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "augment_batch: bad args");
     EOE_CHECK_ARG((mean == nullptr) == (stdv == nullptr), "augment_batch: mean/std must both be given or both NULL");
     EOE_CHECK_ARG(n < (1 << 22) && (size_t)3 * Ho * Wo < (1u << 18) && seed < (1ull << 24) && noise_std >= 0.f,
                   "augment_batch: n < 2^22, 3*Ho*Wo < 2^18, seed < 2^24 (the counter layout of the noise generator)");
-    ProfScope ps("augment_batch", 0, 3.0 * n * Ho * Wo + 12.0 * n * Ho * Wo, stream);
-    size_t g = ((size_t)n * Ho * Wo + 255) / 256;
-    if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(augment_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, params, mean, stdv, out, n, Hs, Ws,
-                       Ho, Wo, flip_first, noise_std, (unsigned long long)seed);
+    ProfScope ps("augment_batch", 0, (double)C * n * Ho * Wo + 4.0 * C * n * Ho * Wo, stream);
+    if (C == 3) {
+        size_t g = ((size_t)n * Ho * Wo + 255) / 256;
+        if (g > 8192) g = 8192;
+        hipLaunchKernelGGL(augment_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, params, mean, stdv, out, n, Hs, Ws,
+                           Ho, Wo, flip_first, noise_std, (unsigned long long)seed);
+    } else {
+        size_t g = ((size_t)n * Ho * ((Wo + 3) / 4) + 255) / 256;
+        if (g > 8192) g = 8192;
+        const bool vec = Wo % 4 == 0 && (uintptr_t)out % 16 == 0;
+        hipLaunchKernelGGL(vec ? augment_c1_kernel<true> : augment_c1_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
+                           src, (long long)n_src, params, mean, stdv, out, n, Hs, Ws, Ho, Wo, flip_first, noise_std, (unsigned long long)seed);
+    }
     EOE_CHECK_LAUNCH("augment_batch");
     return 0;
+}
+
+extern "C" int eoe_augment_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, const float* mean,
+                                 const float* stdv, float* out, int n, int Ho, int Wo, int flip_first, float noise_std,
+                                 uint64_t seed, void* stream) {
+    return eoe_augment_batch_c(src, n_src, Hs, Ws, 3, params, mean, stdv, out, n, Ho, Wo, flip_first, noise_std, seed, stream);
 }
 
 // the crop / flip of eoe_augment_batch alone, uint8 NHWC out: the PIL-stage image that a uint8 filter (the sharpen MSM) sees
@@ -95,16 +201,74 @@ __global__ __launch_bounds__(256) void crop_flip_kernel(const uint8_t* __restric
 }
 }  // namespace
 
-extern "C" int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, uint8_t* out, int n, int Ho,
-                                int Wo, int flip_first, void* stream) {
+extern "C" int eoe_crop_flip_u8_c(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, uint8_t* out, int n,
+                                  int Ho, int Wo, int flip_first, void* stream) {
+    EOE_CHECK_ARG(C == 1 || C == 3, "crop_flip_u8: C must be 1 or 3, not %d", C);
     EOE_CHECK_ARG(src && params && out && n_src > 0 && n > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "crop_flip_u8: bad args");
     EOE_CHECK_ARG((const void*)src != (const void*)out, "crop_flip_u8: out must not alias src");
-    ProfScope ps("crop_flip_u8", 0, 6.0 * n * Ho * Wo, stream);
-    size_t g = ((size_t)n * Ho * Wo + 255) / 256;
-    if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(crop_flip_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, params, out, n, Hs, Ws, Ho, Wo,
-                       flip_first);
+    ProfScope ps("crop_flip_u8", 0, 2.0 * C * n * Ho * Wo, stream);
+    if (C == 3) {
+        size_t g = ((size_t)n * Ho * Wo + 255) / 256;
+        if (g > 8192) g = 8192;
+        hipLaunchKernelGGL(crop_flip_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, params, out, n, Hs, Ws, Ho, Wo,
+                           flip_first);
+    } else {
+        size_t g = ((size_t)n * Ho * ((Wo + 3) / 4) + 255) / 256;
+        if (g > 8192) g = 8192;
+        const bool vec = Wo % 4 == 0 && (uintptr_t)out % 4 == 0;
+        hipLaunchKernelGGL(vec ? crop_flip_c1_kernel<true> : crop_flip_c1_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
+                           src, (long long)n_src, params, out, n, Hs, Ws, Ho, Wo, flip_first);
+    }
     EOE_CHECK_LAUNCH("crop_flip_u8");
+    return 0;
+}
+
+extern "C" int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, uint8_t* out, int n, int Ho,
+                                int Wo, int flip_first, void* stream) {
+    return eoe_crop_flip_u8_c(src, n_src, Hs, Ws, 3, params, out, n, Ho, Wo, flip_first, stream);
+}
+
+// Grayscale(1) (main/train_fmnist.py:32; torchvision hands it to Pillow's Image.convert("L"), libImaging/Convert.c rgb2l): uint8 NHWC
+// [., 3] -> [., 1], L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, byte for byte.  Deterministic and first in the chain, so a resident
+// set is converted once.  A thread takes 16 pixels: three 16-byte loads, one 16-byte store; the pixels past the last whole 16 (all of
+// them when a pointer is not 16-byte aligned) go one per thread.
+namespace {
+__device__ __forceinline__ unsigned rgb_byte(const unsigned* w, int k) { return (w[k >> 2] >> ((k & 3) * 8)) & 255u; }
+
+__global__ __launch_bounds__(256) void grayscale_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n_vec, size_t n_px) {
+    const size_t total = n_vec + (n_px - n_vec * 16);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < n_vec) {
+            const uint4* p = reinterpret_cast<const uint4*>(src) + i * 3;
+            const uint4 q0 = p[0], q1 = p[1], q2 = p[2];
+            const unsigned w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+            unsigned o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const unsigned l = (rgb_byte(w, 3 * k) * 19595u + rgb_byte(w, 3 * k + 1) * 38470u + rgb_byte(w, 3 * k + 2) * 7471u + 0x8000u) >> 16;
+                o[k >> 2] |= l << ((k & 3) * 8);
+            }
+            reinterpret_cast<uint4*>(dst)[i] = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+            const size_t px = n_vec * 16 + (i - n_vec);
+            const uint8_t* p = src + px * 3;
+            dst[px] = (uint8_t)(((unsigned)p[0] * 19595u + (unsigned)p[1] * 38470u + (unsigned)p[2] * 7471u + 0x8000u) >> 16);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int eoe_grayscale_u8(const uint8_t* src, uint8_t* dst, int64_t n_pixels, void* stream) {
+    EOE_CHECK_ARG(src && dst && n_pixels > 0, "grayscale_u8: bad args");
+    EOE_CHECK_ARG((const void*)src != (const void*)dst, "grayscale_u8: dst must not alias src");
+    ProfScope ps("grayscale_u8", 0, 4.0 * (double)n_pixels, stream);
+    const bool aligned = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+    const size_t n_vec = aligned ? (size_t)n_pixels / 16 : 0;
+    const size_t total = n_vec + ((size_t)n_pixels - n_vec * 16);
+    size_t g = (total + 255) / 256;
+    if (g > 16384) g = 16384;
+    hipLaunchKernelGGL(grayscale_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, dst, n_vec, (size_t)n_pixels);
+    EOE_CHECK_LAUNCH("grayscale_u8");
     return 0;
 }
 

@@ -103,41 +103,78 @@ class SyntheticAD:
 # ---------------------------------------------------------------------------------------------------------------------
 # on-device input pipeline
 # ---------------------------------------------------------------------------------------------------------------------
+def _channels(src_u8, who):
+    """the channel count of a uint8 NHWC set, 1 or 3"""
+    C = int(src_u8.shape[3])
+    if C not in (1, 3):
+        raise ValueError(f"{who}: images must have 1 or 3 channels, not {C}")
+    return C
+
+
 def augment_batch(src_u8, params, out_hw, mean=None, std=None, flip_first=True, noise_std=0.001, seed=0):
     """gather + RandomCrop(zero padding) + RandomHorizontalFlip + ToTensor + noise + Normalize in ONE kernel over a uint8
-    NHWC image set resident in HBM (`eoe_augment_batch`, include/eoe_hip.h): replaces the PIL transform chain of
-    `main/train_cifar.py:31-38` / `main/train_clip_imagenet.py:27-36` and the Normalize of `ad_trainer.py:413-425`.
-    src_u8 uint8 [n_src,Hs,Ws,3] (GPU); params int32 [n,4] = (index, top, left, flip) (GPU) -> fp32 NCHW [n,3,Ho,Wo]"""
+    NHWC image set resident in HBM (`eoe_augment_batch_c`, include/eoe_hip.h): replaces the PIL transform chain of
+    `main/train_cifar.py:31-38` / `main/train_clip_imagenet.py:27-36` / `main/train_fmnist.py:31-38` (after its Grayscale) and the
+    Normalize of `ad_trainer.py:413-425`.
+    src_u8 uint8 [n_src,Hs,Ws,C] (GPU), C = 1 or 3; params int32 [n,4] = (index, top, left, flip) (GPU) -> fp32 NCHW [n,C,Ho,Wo];
+    mean / std hold C values"""
     import ctypes as C                                  # noqa: F401
     from ._lib import check, lib
     if not (src_u8.is_cuda and params.is_cuda):
         raise RuntimeError("augment_batch needs GPU tensors (there is no CPU fallback)")
-    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.shape[3] == 3 and src_u8.is_contiguous()
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
+    ch = _channels(src_u8, "augment_batch")
     assert params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous()
     n, (Ho, Wo) = params.shape[0], out_hw
     dev = src_u8.device
     m = torch.as_tensor(mean, dtype=torch.float32, device=dev).contiguous() if mean is not None else None
     s = torch.as_tensor(std, dtype=torch.float32, device=dev).contiguous() if std is not None else None
-    out = torch.empty((n, 3, Ho, Wo), dtype=torch.float32, device=dev)
-    check(lib.eoe_augment_batch(src_u8.data_ptr(), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], params.data_ptr(),
-                                None if m is None else m.data_ptr(), None if s is None else s.data_ptr(), out.data_ptr(), n, Ho, Wo,
-                                1 if flip_first else 0, float(noise_std), int(seed), torch.cuda.current_stream().cuda_stream),
-          "eoe_augment_batch")
+    for name, t in (("mean", m), ("std", s)):
+        if t is not None and t.numel() != ch:
+            raise ValueError(f"augment_batch: {name} must hold one value per channel ({ch}), not {t.numel()}")
+    out = torch.empty((n, ch, Ho, Wo), dtype=torch.float32, device=dev)
+    check(lib.eoe_augment_batch_c(src_u8.data_ptr(), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], ch, params.data_ptr(),
+                                  None if m is None else m.data_ptr(), None if s is None else s.data_ptr(), out.data_ptr(), n, Ho, Wo,
+                                  1 if flip_first else 0, float(noise_std), int(seed), torch.cuda.current_stream().cuda_stream),
+          "eoe_augment_batch_c")
     return out
 
 
 def crop_flip_u8(src_u8, params, out_hw, flip_first=True):
-    """the crop / flip of augment_batch alone (`eoe_crop_flip_u8`: same params, zero padding, both flip orders): uint8 NHWC
-    [n, Ho, Wo, 3], the PIL image the reference's uint8 transforms see between RandomCrop / RandomHorizontalFlip and ToTensor"""
+    """the crop / flip of augment_batch alone (`eoe_crop_flip_u8_c`: same params, zero padding, both flip orders): uint8 NHWC
+    [n, Ho, Wo, C] (C = 1 or 3, as the set), the PIL image the reference's uint8 transforms see between RandomCrop /
+    RandomHorizontalFlip and ToTensor"""
     from ._lib import check, lib
     if not (src_u8.is_cuda and params.is_cuda):
         raise RuntimeError("crop_flip_u8 needs GPU tensors (there is no CPU fallback)")
-    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.shape[3] == 3 and src_u8.is_contiguous()
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
+    ch = _channels(src_u8, "crop_flip_u8")
     assert params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous()
     n, (Ho, Wo) = params.shape[0], out_hw
-    out = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=src_u8.device)
-    check(lib.eoe_crop_flip_u8(src_u8.data_ptr(), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], params.data_ptr(), out.data_ptr(),
-                               n, Ho, Wo, 1 if flip_first else 0, torch.cuda.current_stream().cuda_stream), "eoe_crop_flip_u8")
+    out = torch.empty((n, Ho, Wo, ch), dtype=torch.uint8, device=src_u8.device)
+    check(lib.eoe_crop_flip_u8_c(src_u8.data_ptr(), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], ch, params.data_ptr(),
+                                 out.data_ptr(), n, Ho, Wo, 1 if flip_first else 0, torch.cuda.current_stream().cuda_stream),
+          "eoe_crop_flip_u8_c")
+    return out
+
+
+def grayscale_u8(src_u8):
+    """`transforms.Grayscale(1)` (`main/train_fmnist.py:32`) on a uint8 NHWC colour set [n, H, W, 3] on the GPU -> uint8 [n, H, W, 1],
+    byte-exact with Pillow's `Image.convert("L")` that torchvision calls: L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+    (`eoe_grayscale_u8`).  Deterministic and first in the chain, so a resident set is converted ONCE, not per sample.  A
+    non-contiguous input is made contiguous first (a copy); the result is always a new tensor."""
+    from ._lib import check, lib
+    if not src_u8.is_cuda:
+        raise RuntimeError("grayscale_u8 needs a GPU tensor (there is no CPU fallback)")
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4
+    if src_u8.shape[3] != 3:
+        raise ValueError(f"grayscale_u8: images must have 3 channels, not {src_u8.shape[3]}")
+    src_u8 = src_u8.contiguous()
+    n, H, W, _ = src_u8.shape
+    out = torch.empty((n, H, W, 1), dtype=torch.uint8, device=src_u8.device)
+    if out.numel():
+        check(lib.eoe_grayscale_u8(src_u8.data_ptr(), out.data_ptr(), n * H * W, torch.cuda.current_stream().cuda_stream),
+              "eoe_grayscale_u8")
     return out
 
 
@@ -161,9 +198,10 @@ def resize_u8(src_u8, size, interpolation="bilinear"):
     from ._lib import check, lib, EOE_RESIZE_BILINEAR, EOE_RESIZE_BICUBIC
     if not src_u8.is_cuda:
         raise RuntimeError("resize_u8 needs a GPU tensor (there is no CPU fallback)")
-    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.shape[3] == 3 and src_u8.is_contiguous()
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
     filt = {"bilinear": EOE_RESIZE_BILINEAR, "bicubic": EOE_RESIZE_BICUBIC}[interpolation]
     n, H, W, _ = src_u8.shape
+    ch = _channels(src_u8, "resize_u8")                  # the passes work on [outer, axis, inner] bytes: the channels are `inner`
     if isinstance(size, int):
         Ho, Wo = (int(size * H / W), size) if W <= H else (size, int(size * W / H))
     else:
@@ -172,13 +210,13 @@ def resize_u8(src_u8, size, interpolation="bilinear"):
     cur = src_u8
     if Wo != W:
         b, k, ks = _resize_tables(W, Wo, filt, src_u8.device)
-        nxt = torch.empty((n, H, Wo, 3), dtype=torch.uint8, device=src_u8.device)
-        check(lib.eoe_resize_pass_u8(cur.data_ptr(), nxt.data_ptr(), b.data_ptr(), k.data_ptr(), ks, n * H, W, Wo, 3, st), "eoe_resize_pass_u8")
+        nxt = torch.empty((n, H, Wo, ch), dtype=torch.uint8, device=src_u8.device)
+        check(lib.eoe_resize_pass_u8(cur.data_ptr(), nxt.data_ptr(), b.data_ptr(), k.data_ptr(), ks, n * H, W, Wo, ch, st), "eoe_resize_pass_u8")
         cur = nxt
     if Ho != H:
         b, k, ks = _resize_tables(H, Ho, filt, src_u8.device)
-        nxt = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=src_u8.device)
-        check(lib.eoe_resize_pass_u8(cur.data_ptr(), nxt.data_ptr(), b.data_ptr(), k.data_ptr(), ks, n, H, Ho, Wo * 3, st), "eoe_resize_pass_u8")
+        nxt = torch.empty((n, Ho, Wo, ch), dtype=torch.uint8, device=src_u8.device)
+        check(lib.eoe_resize_pass_u8(cur.data_ptr(), nxt.data_ptr(), b.data_ptr(), k.data_ptr(), ks, n, H, Ho, Wo * ch, st), "eoe_resize_pass_u8")
         cur = nxt
     return cur
 
@@ -191,6 +229,8 @@ def color_jitter_u8(src_u8, idx, factors, order):
     from ._lib import check, lib
     if not src_u8.is_cuda:
         raise RuntimeError("color_jitter_u8 needs GPU tensors (there is no CPU fallback)")
+    if src_u8.dim() != 4 or src_u8.shape[3] != 3:
+        raise ValueError(f"color_jitter_u8: images must have 3 channels, not {src_u8.shape[-1]} (the ops are defined on RGB)")
     dev = src_u8.device
     idx = idx.to(device=dev, dtype=torch.int32).contiguous()
     factors = factors.to(device=dev, dtype=torch.float32).contiguous()
@@ -229,6 +269,16 @@ def clip_preprocess(src_u8, n_px=224):
     return augment_batch(r, p, (n_px, n_px), CLIP_MEAN, CLIP_STD, True, 0.0, 0)
 
 
+def gray_set(images_u8, device):
+    """a resident set under `Grayscale(1)`: `[n, H, W]` is taken as `[n, H, W, 1]`, a 3-channel set is converted once on the
+    device (`grayscale_u8`), a 1-channel set passes through (Grayscale(1) of an `L` image is the identity)"""
+    t = images_u8.unsqueeze(-1) if images_u8.dim() == 3 else images_u8
+    if t.dim() != 4 or t.shape[3] not in (1, 3):
+        raise ValueError(f"grayscale: an image set is [n, H, W], [n, H, W, 1] or [n, H, W, 3], not {list(images_u8.shape)}")
+    t = t.to(device).contiguous()
+    return grayscale_u8(t) if t.shape[3] == 3 else t
+
+
 class ResidentImageSource:
     """step-batch source whose uint8 images live in HBM: every step batch ([normal half | OE half], the BalancedConcatLoader
     contract of `datasets/bases.py:570-600`) is gathered, cropped, flipped, noised and normalised by one kernel; the host only
@@ -244,17 +294,35 @@ class ResidentImageSource:
 
     `normal_index` (optional): the rows of `normal_u8` that ARE the normal training set -- the reference's `Subset` over the
     samples of the normal classes (`bases.py:169-203`); batches report those rows' indices in the full set, as the reference's
-    datasets do (`cifar.py:106-121`), and OE indices are offset by the length of the FULL normal set (`bases.py:596`)."""
+    datasets do (`cifar.py:106-121`), and OE indices are offset by the length of the FULL normal set (`bases.py:596`).
+
+    `grayscale=True` is the 1-channel chain of the 28 x 28 tasks (`main/train_fmnist.py:31-38`: Grayscale(1) -> flip ->
+    RandomCrop(28, padding=3) -> ToTensor -> noise -> 'normalize'): a resident set that arrives with 3 channels is converted once
+    with `grayscale_u8` (Grayscale is deterministic and first in the chain), one that is gray already passes through, as
+    Grayscale(1) of an `L` image is the identity; `[n, H, W]` sets are taken as `[n, H, W, 1]`.  The normal and the OE set may
+    differ in size (28 x 28 and 32 x 32): the crop origin is drawn per half.  Batches are `[., 1, crop, crop]`, statistics have one
+    element.  ColorJitter is defined on RGB and is in no 1-channel chain of the reference: together with `grayscale` it is refused.
+
+    `flip=False` leaves RandomHorizontalFlip out (`main/train_mnist.py`: no flip, no crop, no noise): the flip bits are zeros and
+    NO flip draw is made, as an empty `Compose` draws nothing -- the generator then yields other crop origins in later steps than
+    with `flip=True`, whose draw order is what it always was."""
 
     nominal_label, anomalous_label = 0, 1
 
     def __init__(self, normal_u8, oe_u8, test_u8, test_labels, crop, padding=0, mean=None, std=None, flip_first=True,
                  noise_std=0.001, seed=0, device="cuda", resize=None, test_resize=None, color_jitter=None, interpolation="bilinear",
-                 normal_index=None, normalize=None, ds_statistics=None):
+                 normal_index=None, normalize=None, ds_statistics=None, grayscale=False, flip=True):
         """resize / test_resize: `transforms.Resize` argument applied once to the resident train / test sets (None: as given);
         color_jitter: (brightness, contrast, saturation, hue) of `transforms.ColorJitter`, drawn per sample per step"""
         dev = torch.device(device)
-        self.normal, self.oe, self.test = (t.to(dev).contiguous() for t in (normal_u8, oe_u8, test_u8))
+        if grayscale and color_jitter is not None:
+            raise ValueError("color_jitter works on RGB images and cannot be combined with grayscale=True (no chain of the "
+                             "reference has both)")
+        if grayscale:
+            self.normal, self.oe, self.test = (gray_set(t, dev) for t in (normal_u8, oe_u8, test_u8))
+        else:
+            self.normal, self.oe, self.test = (t.to(dev).contiguous() for t in (normal_u8, oe_u8, test_u8))
+        self.grayscale, self.flip = bool(grayscale), bool(flip)
         if resize is not None:
             self.normal, self.oe = resize_u8(self.normal, resize, interpolation), resize_u8(self.oe, resize, interpolation)
         if test_resize is not None:
@@ -350,7 +418,8 @@ class ResidentImageSource:
         n = len(idx)
         top = torch.randint(-self.padding, Hs + self.padding - self.crop + 1, (n,), generator=self._g)
         left = torch.randint(-self.padding, Ws + self.padding - self.crop + 1, (n,), generator=self._g)
-        flip = torch.randint(0, 2, (n,), generator=self._g)
+        # flip=False: no RandomHorizontalFlip in the chain, so no draw (the class docstring)
+        flip = torch.randint(0, 2, (n,), generator=self._g) if self.flip else torch.zeros(n, dtype=torch.int64)
         return torch.stack([idx.to(torch.int64), top, left, flip], dim=1).to(torch.int32)
 
     def _epoch(self, batch_size):
@@ -441,12 +510,20 @@ class LabelledImageSet:
     classes x 2 seeds does not copy the set 60 times."""
 
     def __init__(self, train_u8, train_classes, test_u8, test_classes, oe_u8, classes, crop, device="cuda", normalize=None,
-                 **source_kw):
+                 grayscale=False, **source_kw):
         """normalize: one of the reference's transform strings ('normalize', 'gcn-normalize', ...): every task then gets the
         statistics of ITS normal classes (`bases.py:293-372`), fitted once per class set and kept (the reference keeps them in
-        `stats_cache.json`, `bases.py:374-410`): thirty classes x two seeds fit thirty times"""
+        `stats_cache.json`, `bases.py:374-410`): thirty classes x two seeds fit thirty times.
+        grayscale: the 1-channel chain of `ResidentImageSource(grayscale=True)`; colour sets are converted here, once for all
+        tasks.  `flip=False` and the other options of the source go through `source_kw`."""
         dev = torch.device(device)
-        self.train, self.test, self.oe = (t.to(dev).contiguous() for t in (train_u8, test_u8, oe_u8))
+        if grayscale:
+            if source_kw.get("color_jitter") is not None:
+                raise ValueError("color_jitter works on RGB images and cannot be combined with grayscale=True")
+            self.train, self.test, self.oe = (gray_set(t, dev) for t in (train_u8, test_u8, oe_u8))
+            source_kw = dict(source_kw, grayscale=True)
+        else:
+            self.train, self.test, self.oe = (t.to(dev).contiguous() for t in (train_u8, test_u8, oe_u8))
         self.train_classes = torch.as_tensor(train_classes, dtype=torch.int64).clone()
         self.test_classes = torch.as_tensor(test_classes, dtype=torch.int64).clone()
         self.classes = list(classes)

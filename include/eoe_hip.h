@@ -853,6 +853,22 @@ int eoe_focal_bwd(const float* x, const int64_t* labels, const float* gscale, fl
 int eoe_augment_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, const int32_t* params, const float* mean,
                       const float* std, float* out, int n, int Ho, int Wo, int flip_first, float noise_std, uint64_t seed,
                       void* stream);
+/* The same pipeline for C = 1 or 3 channels (C = 1: the 28 x 28 tasks, main/train_fmnist.py:31-38, main/train_mnist.py), and
+ * Grayscale(1), the first transform of the Fashion-MNIST chain, for the resident colour OE set.
+ *   eoe_augment_batch_c  eoe_augment_batch on src uint8 [n_src, Hs, Ws, C] -> fp32 NCHW [n, C, Ho, Wo]; mean / std hold C floats.
+ *                        The noise rule is unchanged: with C = 1 the element is e = y*Wo + x, the draws of channel 0 of the
+ *                        3-channel form.  C = 3 is eoe_augment_batch itself.  With C = 1 a slot whose source index lies outside
+ *                        [0, n_src) reads nothing and comes out as padding.
+ *   eoe_crop_flip_u8_c   eoe_crop_flip_u8 on [n_src, Hs, Ws, C] -> uint8 [n, Ho, Wo, C], C = 1 or 3
+ *   eoe_grayscale_u8     dst[p] = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 of the n_pixels RGB pixels of src (uint8, 3 bytes per
+ *                        pixel -> 1 byte per pixel): Pillow's Image.convert("L"), byte for byte.  Out of place; any alignment
+ *                        (16-byte aligned pointers take the 16-pixels-per-thread path).  Deterministic: convert a resident set once. */
+int eoe_augment_batch_c(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, const float* mean,
+                        const float* std, float* out, int n, int Ho, int Wo, int flip_first, float noise_std, uint64_t seed,
+                        void* stream);
+int eoe_crop_flip_u8_c(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, uint8_t* out, int n, int Ho,
+                       int Wo, int flip_first, void* stream);
+int eoe_grayscale_u8(const uint8_t* src, uint8_t* dst, int64_t n_pixels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
