@@ -488,6 +488,8 @@ class VitEmbedFunction(torch.autograd.Function):
 
 
 _BLOCK_PARAMS = ("ln1_g", "ln1_b", "w_in", "b_in", "w_out", "b_out", "ln2_g", "ln2_b", "w_fc", "b_fc", "w_proj", "b_proj")
+_BLOCK_WEIGHTS = (2, 4, 8, 10)                        # their places in it: the four matrices,
+_BLOCK_VECTORS = (0, 1, 3, 5, 6, 7, 9, 11)            # the eight bias and LayerNorm vectors
 
 
 def _block_ws(M, D, device, dtype):
@@ -516,40 +518,71 @@ VIT_DEFER_FINISH = os.environ.get("EOE_VIT_DEFER_FINISH", "1") != "0"
 # points; measured, it moves nothing (10.392 / 10.377 against 10.398 / 10.403 ms per step, two interleaved pairs on one box: the stalls are the
 # profiler's), so the default stays at 1 and the third set of buffers (180 MB) is not taken
 VIT_ASYNC_LAG = int(os.environ.get("EOE_VIT_ASYNC_LAG", "1"))
-_vit_red_table = _lib.RedTable()
 _vit_args_cache = {}          # id(w_in) -> (signature, the static part of the block's eoe_vit_block_fwd_args as bytes)
-_vit_red_seq = 0
-_vit_red_stream = None        # the stream the current sweep's blocks were enqueued on
 VIT_RED_POOL = 16
-_vit_handoff = None
-_vit_parity = 0
-_vit_pending = None
-_vit_deferred_hook = None
+
+
+def _late_write_ok(params, needs):
+    """may the gradients of `params` (with their `needs_input_grad` flags) be written AFTER backward() has returned them -- by the end-of-pass
+    flush (VIT_DEFER_FINISH) or on the side stream (VIT_ASYNC_WGRAD)?"""
+    # Only where autograd's AccumulateGrad adopts the returned tensor as p.grad: a leaf that requires a gradient, is asked for one and has none
+    # yet, and no arena hook that sends a gradient the moment autograd has it (async_wgrad_blockers).  Anywhere else -- gradient accumulation,
+    # zero_grad(set_to_none=False), a frozen parameter under a trainable input, autograd.grad on a subset -- autograd reads the tensor at once
+    # (p.grad += g) and frees it, and the late kernel would write into memory the allocator may have handed out again.  Holding the returned
+    # tensors until the flush does NOT make those cases safe: a gradient that something else still references is not adopted but cloned, so
+    # the late write lands in the orphan and p.grad keeps uninitialised memory.
+    return async_wgrad_blockers == 0 and all(need and p.is_leaf and p.requires_grad and p.grad is None for p, need in zip(params, needs))
+
+
+class _VitSweep:
+    """what the blocks of one backward sweep share, per (device, stream).  `task` is autograd's id of the backward() call that owns it
+    (torch._C._current_graph_task_id(): -1 outside backward, one id per call inside, end-of-pass callbacks included): whatever a sweep still
+    holds under another id was left by a pass that died before its callback, and is dropped, never launched."""
+
+    def __init__(self, stream):
+        self.table = _lib.RedTable()      # the finish reductions left for the one flush at the end of the pass (VIT_DEFER_FINISH)
+        self.stream = stream              # where the sweep's kernels run, and so its flush (see vit_flush_finish)
+        self.task = -1
+        self.parity = 0                   # which set of alternating scratch buffers the next block takes
+        self.deferred = self.finished_per_block = self.wgrad_async = self.wgrad_inline = 0      # blocks by form; reset by whoever reads them
+        self.pending = None               # the activations that weight-gradient launches in flight still read (kept across reset(): the
+        self.reset()                      # next block call, or the join in front of it, orders the stream behind a dead pass's launches)
+
+    def reset(self):
+        self.table.count = 0
+        self.seq = 0                      # the next block's `vit_red_seq*` scratch
+        self.handoff = None               # the previous block's hand-over record
+
+    def flush(self):
+        self.seq = 0
+        if self.table.count:
+            check(lib.eoe_red_table_flush(C.byref(self.table), self.stream), "eoe_red_table_flush")
+
+
+_vit_sweeps = {}              # (device index, raw stream) -> _VitSweep
+
+
+def _vit_live_sweeps():
+    task = torch._C._current_graph_task_id()
+    return [sw for sw in _vit_sweeps.values() if sw.task == task]
 
 
 def vit_flush_finish():
     """launches the finish reductions the blocks of this backward sweep left in the table (VIT_DEFER_FINISH); called by the autograd engine
-    at the end of the pass, harmless at any other time"""
-    global _vit_red_seq
-    _vit_red_seq = 0
-    if _vit_red_table.count:
-        # on the stream the sweep's kernels ran on (the engine runs this callback in the thread that called backward(), whose current stream may
-        # be another one; the engine orders that stream behind the sweep's only AFTER the callbacks)
-        st = _vit_red_stream if _vit_red_stream is not None else _stream()
-        check(lib.eoe_red_table_flush(C.byref(_vit_red_table), st), "eoe_red_table_flush")
+    at the end of the pass.  At any other time it does nothing: what a sweep of another pass holds is not this caller's to launch"""
+    # each on the stream its sweep's kernels ran on (the engine runs this callback in the thread that called backward(), whose current stream
+    # may be another one; the engine orders that stream behind the sweep's only AFTER the callbacks)
+    for sw in _vit_live_sweeps():
+        sw.flush()
 
 
 def vit_side_join():
     """orders the current stream behind the last asynchronous weight-gradient launch and releases what it was reading; called by the
     autograd engine at the end of a backward pass that used the asynchronous path (and harmless at any other time)"""
-    global _vit_pending, _vit_deferred_hook
     vit_flush_finish()
     check(lib.eoe_vit_side_join(_stream()), "eoe_vit_side_join")
-    _vit_pending = None
-    if _vit_deferred_hook is not None:                     # the last block of the sweep: its bucket goes out behind the join
-        prev, _vit_deferred_hook = _vit_deferred_hook, None
-        prev()
-
+    for sw in _vit_live_sweeps():
+        sw.pending = None
 
 
 # the last block of the vision tower computes only what its single reader -- ln_post on the class token (clip/model.py:231-232) -- uses
@@ -599,15 +632,17 @@ class VitBlockFunction(torch.autograd.Function):
         a.xn1, a.qkv, a.att, a.xn2, a.hpre, a.hact = (ptr[k] for k in ("xn1", "qkv", "att", "xn2", "hpre", "hact"))
         a.stats1, a.stats2 = ptr["stats1"], ptr["stats2"]
         a.cls_only = 1 if cls_only else 0
-        if _vit_red_table.count:                 # jobs of a backward pass that died before its end-of-pass flush: their scratch is about to be reused
-            _vit_red_table.count = 0
+        sw = _vit_sweeps.get((x.device.index, _stream()))
+        if sw is not None and sw.table.count and sw.task != torch._C._current_graph_task_id():
+            sw.table.count = 0          # jobs of a backward pass that died before its flush (a forward INSIDE the live pass leaves them alone)
         keep = any(ctx.needs_input_grad)            # (grad mode itself is always off inside a Function's forward)
         if not keep:
             a.hpre = None          # forward only (frozen encoder, scoring): the MLP's pre-activation is not kept (79 MB per block)
         check(lib.eoe_vit_block_fwd(C.byref(a), _stream()), "eoe_vit_block_fwd")
         ctx.save_for_backward(x, ws, ln1_g, ln1_b, w_in, b_in, w_out, b_out, ln2_g, ln2_b, w_fc, b_fc, w_proj, b_proj)
         ctx.args = a
-        ctx.shadows = sh          # keep the 16-bit copies used by this forward alive until backward
+        ctx.shadows = sh          # keep the 16-bit copies used by this forward alive until backward,
+        ctx.sk_ws = sk_ws         # and the workspace `a` points to (not cached while a stream is being captured)
         return x_out
 
     @staticmethod
@@ -628,30 +663,37 @@ class VitBlockFunction(torch.autograd.Function):
         b.g_b_in, b.g_b_out, b.g_b_fc, b.g_b_proj = (_p(grads[k]) for k in ("b_in", "b_out", "b_fc", "b_proj"))
         b.g_w_in, b.g_w_out, b.g_w_fc, b.g_w_proj = (_p(grads[k]) for k in ("w_in", "w_out", "w_fc", "w_proj"))
         b.accumulate = 0
+        stream, task = _stream(), torch._C._current_graph_task_id()
+        sw = _vit_sweeps.get((dev.index, stream))
+        if sw is None:
+            sw = _vit_sweeps[(dev.index, stream)] = _VitSweep(stream)
+        if sw.task != task:                                # what it holds was left by a pass that never reached its callback
+            sw.reset()
+            sw.task = task
         # hand-over between consecutive blocks of the backward sweep (eoe_hip.h, eoe_vit_block_bwd_args): this block's LayerNorm-1 backward
         # also writes the 16-bit copy of dx_in and leaves its column sums in its partial rows -- what the next block to run would compute
         # with a pass of its own (eoe_cast_colsum).  Two alternating sets of (copy, reduction scratch): the previous call's are still read.
-        global _vit_handoff, _vit_parity
-        par = _vit_parity = (_vit_parity + 1) % (3 if VIT_ASYNC_LAG >= 2 else 2)      # (async_wgrad = 2: a launch's buffers rest until two later calls have returned)
-        h = _vit_handoff
-        _vit_handoff = None
+        par = sw.parity = (sw.parity + 1) % (3 if VIT_ASYNC_LAG >= 2 else 2)      # (async_wgrad = 2: a launch's buffers rest until two later calls have returned)
+        h, sw.handoff = sw.handoff, None
         d16_next = scratch(f"d16_next{par}", (M, D), dt, dev)
         b.next_d16 = _p(d16_next) if VIT_HANDOVER else None
-        if (h is not None and h["dx"] is dx_out and dx_out._version == h["version"] and h["shape"] == (M, D, ctx.args.n) and h["dt"] == dt
-                and h["stream"] == _stream()):
+        if h is not None and h["dx"] is dx_out and dx_out._version == h["version"] and h["shape"] == (M, D, ctx.args.n) and h["dt"] == dt:
             b.in_d16, b.in_red_scratch = _p(h["d16"]), _p(h["red"])
         # asynchronous weight gradients (eoe_hip.h, eoe_vit_block_bwd_args.async_wgrad): the block's grouped wgrad launch goes to the
         # library's side stream and runs under the NEXT block's kernels.  What it reads -- dh, dqkv, d16_c, the dY of c_proj and the saved
-        # activations in `ws` -- must outlive this call: two alternating sets of those scratch buffers (`par`), `ws` parked in `_vit_pending`
+        # activations in `ws` -- must outlive this call: two alternating sets of those scratch buffers (`par`), `ws` parked in `sw.pending`
         # until the next block's call has returned (it orders the stream behind this launch), and one join when the backward pass ends.
         hook = grad_ready_hooks.get(id(params["ln1_g"]))
         has_hook = hook is not None and hook[0]() is params["ln1_g"]
-        # (a data-parallel bucket hook of this block wants its weight gradients: with the asynchronous launch it is fired one block later --
-        #  after the next block's call, which orders the stream behind this block's launch -- or by the join at the end of the pass)
-        use_async = VIT_ASYNC_WGRAD and not torch.cuda.is_current_stream_capturing()
-        # 2: this call waits for the launch before the previous one only (eoe_hip.h); a data-parallel bucket hook reads the previous block's weight
-        # gradients right behind this call, so with one installed the call orders the stream behind the previous launch as before (1)
-        b.async_wgrad = (1 if has_hook or VIT_ASYNC_LAG == 1 else 2) if use_async else 0
+        # (a data-parallel bucket hook of this block reads its gradients right behind this call: everything in line then; and otherwise
+        #  only where the side stream may write the four weight gradients after this call has returned them)
+        capturing = torch.cuda.is_current_stream_capturing()
+        ps, need = saved[2:], ctx.needs_input_grad[3:]
+        use_async = (VIT_ASYNC_WGRAD and not has_hook and not capturing
+                     and _late_write_ok([ps[i] for i in _BLOCK_WEIGHTS], [need[i] for i in _BLOCK_WEIGHTS]))
+        if not use_async and sw.pending is not None:       # behind asynchronous blocks of this pass: nothing else orders the stream behind
+            check(lib.eoe_vit_side_join(stream), "eoe_vit_side_join")      # their launches before their buffers come round again
+        b.async_wgrad = (1 if VIT_ASYNC_LAG == 1 else 2) if use_async else 0      # 2: waits for the launch before the previous one only (eoe_hip.h)
         b.d16_a = _p(scratch(f"d16_a{par}", (M, D), dt, dev))
         b.d16_b = _p(scratch("d16_b", (M, D), dt, dev))
         b.d16_c = _p(scratch(f"d16_c{par}", (M, D), dt, dev))
@@ -659,42 +701,36 @@ class VitBlockFunction(torch.autograd.Function):
         b.dqkv = _p(scratch(f"dqkv{par}", (M, 3 * D), dt, dev))
         b.dx_mid = _p(scratch("dx_mid", (M, D), torch.float32, dev))
         nred = (M + 63) // 64 * 4 * D + 2 * LN_SCRATCH_ROWS * 3 * D + ctx.args.n * 3 * D + 256 * D          # EOE_VIT_RED_SCRATCH(n, L, D)
-        # deferred finish: every block of the sweep keeps its own partial rows until the one flush at the end of the pass
-        global _vit_red_seq
-        defer = VIT_DEFER_FINISH and not has_hook and not torch.cuda.is_current_stream_capturing()
+        # deferred finish: every block of the sweep keeps its own partial rows until the one flush at the end of the pass, which writes the
+        # eight bias / LayerNorm gradients after this call has returned them; where it may not, the block finishes its own before the return
+        defer = (VIT_DEFER_FINISH and not has_hook and not capturing
+                 and _late_write_ok([ps[i] for i in _BLOCK_VECTORS], [need[i] for i in _BLOCK_VECTORS]))
         if defer:
-            global _vit_red_stream
-            _vit_red_stream = _stream()
-            red = scratch(f"vit_red_seq{_vit_red_seq % VIT_RED_POOL}", (nred,), torch.float32, dev)
-            _vit_red_seq += 1
-            if _vit_red_seq >= VIT_RED_POOL:               # a deeper tower than the pool: launch what is queued before a scratch comes round again
-                vit_flush_finish()
-            b.red_table = C.pointer(_vit_red_table)
+            red = scratch(f"vit_red_seq{sw.seq % VIT_RED_POOL}", (nred,), torch.float32, dev)
+            sw.seq += 1
+            if sw.seq >= VIT_RED_POOL:                     # a deeper tower than the pool: launch what is queued before a scratch comes round again
+                sw.flush()
+            b.red_table = C.pointer(sw.table)
         else:
             red = scratch(f"vit_red{par}", (nred,), torch.float32, dev)
         b.red_scratch = _p(red)
         sk_bytes = torch.cuda.get_device_properties(dev).multi_processor_count * (256 * 256 * 4)      # EOE_TN_STREAMK_WORKSPACE_BYTES
         b.tn_workspace, b.tn_workspace_bytes = _p(scratch("tn_streamk", (sk_bytes,), torch.uint8, dev)), sk_bytes
-        check(lib.eoe_vit_block_bwd(C.byref(b), _stream()), "eoe_vit_block_bwd")
+        check(lib.eoe_vit_block_bwd(C.byref(b), stream), "eoe_vit_block_bwd")
+        sw.deferred, sw.finished_per_block = sw.deferred + defer, sw.finished_per_block + (not defer)
+        sw.wgrad_async, sw.wgrad_inline = sw.wgrad_async + use_async, sw.wgrad_inline + (not use_async)
         if VIT_HANDOVER:
-            _vit_handoff = dict(dx=dx_in, version=dx_in._version, shape=(M, D, ctx.args.n), dt=dt, stream=_stream(), d16=d16_next, red=red)
-        global _vit_pending, _vit_deferred_hook
+            sw.handoff = dict(dx=dx_in, version=dx_in._version, shape=(M, D, ctx.args.n), dt=dt, d16=d16_next, red=red)
         # what the launches still in flight read: this call's and the previous call's (the call before that has been ordered behind by now)
-        _vit_pending = ((x, ws), _vit_pending[0] if _vit_pending else None) if use_async else None
-        if _vit_deferred_hook is not None:                 # the previous block's bucket: its weight gradients are complete in stream order now
-            prev, _vit_deferred_hook = _vit_deferred_hook, None
-            prev()
+        sw.pending = ((x, ws), sw.pending[0] if sw.pending else None) if use_async else None
         if use_async:
             # runs when this backward pass is complete; queued by every block (idempotent): a flag "already queued" would survive a pass
             # that died with an exception and leave the next pass without its join
             torch.autograd.Variable._execution_engine.queue_callback(vit_side_join)
         elif defer:
             torch.autograd.Variable._execution_engine.queue_callback(vit_flush_finish)
-        if has_hook:      # (weakref to the parameter, callable): the bucket's all-reduce reads this block's weight gradients
-            if use_async:
-                _vit_deferred_hook = hook[1]
-            else:
-                hook[1]()
+        if has_hook:      # (weakref to the parameter, callable): the bucket's all-reduce reads this block's gradients
+            hook[1]()
         return (dx_in, None, None) + tuple(grads[k] for k in _BLOCK_PARAMS) + (None,)
 
 

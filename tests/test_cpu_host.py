@@ -265,3 +265,31 @@ def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
     assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
     loss = np.load(tmp_path / "a" / "loss.npy")
     assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 0.5
+
+
+def test_late_gradient_writes_only_into_tensors_autograd_adopts():
+    """ops._late_write_ok, the one rule for writing a gradient after backward() has returned it (the deferred finish, the asynchronous
+    weight gradients): every parameter a leaf that requires a gradient, is asked for one and has none yet, and no arena hooks installed"""
+    from eoe_amd import ops
+
+    def leaves(n=3):
+        return [torch.zeros(4, requires_grad=True) for _ in range(n)]
+
+    assert ops._late_write_ok(leaves(), [True] * 3)
+    ps = leaves()
+    ps[1].grad = torch.zeros(4)                                   # gradient accumulation, zero_grad(set_to_none=False), a second backward()
+    assert not ops._late_write_ok(ps, [True] * 3)
+    ps = leaves()
+    ps[2].requires_grad_(False)                                   # frozen
+    assert not ops._late_write_ok(ps, [True] * 3)
+    ps = leaves()
+    ps[0] = ps[0] * 2                                             # not a leaf: autograd passes its gradient on, nothing adopts it
+    assert ps[0].requires_grad and not ops._late_write_ok(ps, [True] * 3)
+    assert not ops._late_write_ok(leaves(), [True, False, True])  # autograd.grad on a subset
+    old = ops.async_wgrad_blockers
+    ops.async_wgrad_blockers = 1
+    try:
+        assert not ops._late_write_ok(leaves(), [True] * 3)
+    finally:
+        ops.async_wgrad_blockers = old
+    assert ops._late_write_ok(leaves(), [True] * 3)
