@@ -23,6 +23,9 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     `ds_statistics` stored in the file.  The reference only takes the statistics from the file there and scores a freshly reset
     model (:257-264), which makes "score this snapshot again" impossible without training; a module handed in through `load` is
     scored as is, as in the reference.
+  * `curves=True` makes the trainer keep what the reference always keeps: the whole ROC of a training epoch (the last one is returned) and the ROC and
+    precision-recall curve of the evaluation (:452-455, 516-522), counted on the device (`eoe_rank_curves`), and the per-class
+    "mean" curves (`logger.py:94-122`) in `trainer.curves`.  The default keeps the scores alone and does nothing else.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -35,7 +38,7 @@ import numpy as np
 import torch
 
 from .. import ops, parallel
-from ..metrics import ROC, PRC, roc_auc, average_precision, auc_ap_device
+from ..metrics import ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve
 from ..msm import apply_msms, check_supported
 from ..normalize import GcnNormalize
 from ..optim import FusedAdam
@@ -97,10 +100,20 @@ class ADTrainer(ABC):
                  wdk: float = 0.0, milestones: List[int] = (), batch_size: int = 128, ad_mode: str = "one_vs_rest",
                  device: Union[str, torch.device] = "cuda", oe_limit_samples=np.inf, oe_limit_classes=np.inf,
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
-                 graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto"):
+                 graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
-        `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0")."""
+        `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
+
+        `curves=True`: the ROC / PRC containers that `train_cls` and `eval_cls` return carry their curves (`tpr` / `fpr` / `ths`,
+        `prec` / `rec` / `ths`), and `run` leaves `self.curves` = {'train_rocs', 'eval_rocs', 'eval_prcs': [class][seed] containers,
+        'mean_train_rocs', 'mean_eval_rocs', 'mean_eval_prcs': [class] `mean_plot` of the seeds that produced one, else None} and
+        logs each evaluation's curves as `eval_cls{c}_it{seed}_roc` / `_prc`.  `mean_plot` thins the curves with `np.random.choice`:
+        after each class `run` makes the reference's draws in the reference's order (training ROC, evaluation ROC, evaluation
+        PRC; `ad_trainer.py:308-313`).  The reference's intermediate plots after every seed (`:283, 295-296`) draw from `np.random`
+        as well whenever a class has more than one curve; those draws are NOT replayed, so from the second seed of a class on the
+        generator is not where the reference's is.  With `curves=False` (the default) nothing of this runs: no extra launch, no
+        draw, the same return values and files as before."""
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
         # launch-bound small encoders (CNN32 at 32x32); single GPU only, ragged batches run eagerly
@@ -134,6 +147,8 @@ class ADTrainer(ABC):
         check_supported(self.msms, self.device)          # sharpen on a CPU device raises NotImplementedError
         self._step_msms = self.msms                         # the train MSMs left to the step batch (_msm_source)
         self._gcn = None                                    # the task's GcnNormalize, if its source is in that mode (_normalize_hook)
+        self.with_curves = bool(curves)
+        self.curves = None                                  # filled by run() when with_curves
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -245,6 +260,7 @@ class ADTrainer(ABC):
         assert self.ds is None or len(wanted) == 1, "pre-loading DS (setting trainer.ds to something) only allowed for one class"
         models, train_rocs = [[] for _ in range(n_cls)], [[] for _ in range(n_cls)]
         eval_rocs, eval_prcs = [[] for _ in range(n_cls)], [[] for _ in range(n_cls)]
+        means = {k: [None] * n_cls for k in ("mean_train_rocs", "mean_eval_rocs", "mean_eval_prcs")}
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
@@ -260,10 +276,19 @@ class ADTrainer(ABC):
                     roc, prc = self.eval_cls(model, ds, c, cstr, seed)
                 eval_rocs[c].append(roc)
                 eval_prcs[c].append(prc)
+                if self.with_curves and roc is not None:
+                    self.logger.logjson(f"eval_cls{c}_it{seed}_roc", {"fpr": roc.fpr.tolist(), "tpr": roc.tpr.tolist(),
+                                                                      "ths": roc.ths.tolist(), "auc": roc.auc})
+                    self.logger.logjson(f"eval_cls{c}_it{seed}_prc", {"prec": prc.prec.tolist(), "rec": prc.rec.tolist(),
+                                                                      "ths": prc.ths.tolist(), "avg_prec": prc.avg_prec})
                 if model is not None:
                     self.logger.snapshot(f"snapshot_cls{c}_it{seed}", model, epoch=self.epochs,
                                          ds_statistics=getattr(ds, "ds_statistics", None))
                 models[c].append(model if (model is None or ADTrainer.KEEP_SNAPSHOT_IN_RAM) else None)
+            if self.with_curves:
+                # the seeds' "mean" curves of this class, in the reference's order (:308-313; plot_many skips the seeds without a curve)
+                for k, lst in (("mean_train_rocs", train_rocs[c]), ("mean_eval_rocs", eval_rocs[c]), ("mean_eval_prcs", eval_prcs[c])):
+                    means[k][c] = mean_plot([r for r in lst if r is not None])
 
         def per_class(curves, attr):
             """mean over the seeds of each class that produced a curve"""
@@ -278,6 +303,8 @@ class ADTrainer(ABC):
             if aps:
                 mean_avg_prec = float(np.mean(aps))
             self.logger.logtxt(f"Eval: Overall {mean_auc * 100:04.2f}% +- {std_auc * 100:04.2f}% AUC.")
+        if self.with_curves:
+            self.curves = {"train_rocs": train_rocs, "eval_rocs": eval_rocs, "eval_prcs": eval_prcs, **means}
         cls_aucs = [[None if r is None else r.get_score() for r in lst] for lst in eval_rocs]
         self.logger.logjson("results", {"eval_mean_auc": mean_auc, "eval_std_auc": std_auc,
                                         "eval_mean_avg_prec": mean_avg_prec, "eval_cls_rocs": cls_aucs,
@@ -455,6 +482,9 @@ class ADTrainer(ABC):
                 if bool((la == 1).any()):
                     # the epoch's AUC from the GPU-resident scores (eoe_auc_ap: exact pair counts), no host copy of the scores
                     cls_roc = ROC(auc_ap_device(la, sc)[0] if sc.is_cuda else roc_auc(la.cpu().numpy(), sc.cpu().numpy()))   # :452-455
+                    if self.with_curves:                          # every epoch, as the reference: the last one with anomalies is returned
+                        cls_roc.fpr, cls_roc.tpr, cls_roc.ths = roc_curve(la if sc.is_cuda else la.cpu().numpy(),
+                                                                          sc if sc.is_cuda else sc.cpu().numpy())
                 sched.step()                                                                            # :468
         finally:
             ops.set_grad_scale(prev_scale)
@@ -504,6 +534,12 @@ class ADTrainer(ABC):
             else:
                 auc, ap = roc_auc(la, sc), average_precision(la, sc)
             cls_roc, cls_prc = ROC(auc), PRC(ap)
+            if self.with_curves:                       # one eoe_rank_curves call serves both (ad_trainer.py:517, 520)
+                if sc_t.is_cuda:
+                    (cls_roc.fpr, cls_roc.tpr, cls_roc.ths), (cls_prc.prec, cls_prc.rec, cls_prc.ths) = curves_device(la_t, sc_t)
+                else:
+                    cls_roc.fpr, cls_roc.tpr, cls_roc.ths = roc_curve(la, sc)
+                    cls_prc.prec, cls_prc.rec, cls_prc.ths = precision_recall_curve(la, sc)
             self.logger.logtxt(f'Eval: class "{clsstr}" yields {cls_roc.auc * 100:04.2f}% AUC and '
                                f'{cls_prc.avg_prec * 100:04.2f}% average precision (seed {seed}).')
         else:

@@ -817,6 +817,23 @@ int eoe_avgpool_bwd(const float* dout, float* dx, int n, int HW, int C, void* st
  * (n^2 compares, no sort).  scratch: EOE_AUC_SCRATCH_BYTES(n) bytes. */
 #define EOE_AUC_SCRATCH_BYTES(n) ((size_t)(((n) + 255) / 256) * 24)
 int eoe_auc_ap(const float* scores, const int64_t* labels, int64_t positive_label, double* out, void* scratch, int n, void* stream);
+/* The curves behind those two numbers (ad_trainer.py:453, 517, 520: sklearn's roc_curve and precision_recall_curve; the containers
+ * logger.py:36-91 keep them).  For the K distinct scores thr_0 > thr_1 > ... > thr_{K-1}:
+ *     out_tps[k] = #{j: labels[j] == positive_label, scores[j] >= thr_k},   out_fps[k] = #{j: scores[j] >= thr_k} - out_tps[k]
+ * exact integers, from pair counts (n^2 compares, no sort, no atomics); out_thr[k] carries the bits of the element with the smallest
+ * index among its equal scores (what a reversed stable sort keeps; -0.0 == 0.0 is one group).  out_roc_* hold the same table without
+ * the slots roc_curve's drop_intermediate removes: when drop_intermediate != 0 and K > 2, slot k with 0 < k < K-1 stays iff the second
+ * difference of fps or of tps at k is not 0; otherwise the whole table.  out_counts[0] = K, out_counts[1] = K_roc.  The rates
+ * (fps / fps[K-1], tps / tps[K-1], tps / (tps + fps)) are left to the caller.
+ *   scores fp32 [n], labels int64 [n]; out_fps / out_tps / out_roc_fps / out_roc_tps int64 [n], out_thr / out_roc_thr fp32 [n] (the
+ *   first K resp. K_roc entries are written), out_counts int32 [2]; all DEVICE, no two of them overlapping.  1 <= n <= 2^20.
+ *   Non-finite scores are the caller's to reject (NaN compares false with everything; nothing is written out of range).
+ *   scratch: eoe_rank_curves_scratch_bytes(n) bytes (0 for an n outside the range), 4-byte aligned.  Four enqueues on `stream`
+ *   (a memset and three launches); K stays on the device in between. */
+size_t eoe_rank_curves_scratch_bytes(int n);
+int eoe_rank_curves(const float* scores, const int64_t* labels, int64_t positive_label, int n, int drop_intermediate,
+                    int64_t* out_fps, int64_t* out_tps, float* out_thr, int64_t* out_roc_fps, int64_t* out_roc_tps, float* out_roc_thr,
+                    int32_t* out_counts, void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
