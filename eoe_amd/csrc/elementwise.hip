@@ -912,11 +912,20 @@ __global__ __launch_bounds__(256) void clip_bwd_kernel(const float* __restrict__
     const float coef = inv_count * (gscale ? gscale[0] : 1.0f);
     float g = (pick < 0 || lane >= T) ? 0.f : (p - (lane == pick ? 1.f : 0.f));
     const float gl = wave_sum(lane < T ? g * l : 0.f);
-    for (int c = lane; c < d; c += 64) {
+    // the trip count is wave-uniform: in a ragged tail (d % 64 != 0) lane j < T may own no column, and a shuffle reads nothing
+    // from a lane that has left the loop
+    for (int c0 = 0; c0 < d; c0 += 64) {
+        const int c = c0 + lane;
+        const bool live = c < d;
         float acc = 0.f;
-        for (int j = 0; j < T; ++j) acc += __shfl(g, j, 64) * text[(size_t)j * d + c];
-        const float fh = f[(size_t)row * d + c] * inv_norm;
-        df[(size_t)row * d + c] = coef * (100.0f * acc - fh * gl) * inv_norm;
+        for (int j = 0; j < T; ++j) {
+            const float gj = __shfl(g, j, 64);
+            if (live) acc += gj * text[(size_t)j * d + c];
+        }
+        if (live) {
+            const float fh = f[(size_t)row * d + c] * inv_norm;
+            df[(size_t)row * d + c] = coef * (100.0f * acc - fh * gl) * inv_norm;
+        }
     }
 }
 
