@@ -217,12 +217,13 @@ __global__ __launch_bounds__(256) void stem_unpack_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------- BatchNorm
-// column sums of y and y^2 over M rows, y fp32 [M, C]: workgroup (bx, by) writes its partial sums (accumulated in double)
+// column sums of y and y^2 over M rows, y fp32 [M, C]: workgroup (bx, by) writes its partial sums (accumulated and kept in double:
+// rounded to float, sum y^2 lost the spread of a channel whose mean is several times its deviation -- rstd off by 2e-6 at mean = 8 std)
 // to row by of part[gridDim.y][2C] -- no atomics (device-scope float atomics from 8 XCDs cost ~80 us per call here,
 // more than the streaming pass itself), no zero-init; bn_finalize_kernel adds the rows up.  VEC = 4: a thread owns 4 adjacent channels (16-B loads), cpb
 // thread-columns x rpb row lanes per workgroup; VEC = 1 for C not a multiple of 4 (the 1-channel gate BatchNorm).
 template <int VEC>
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y, float* __restrict__ part, int M, int C, int cpb) {
+__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y, double* __restrict__ part, int M, int C, int cpb) {
     __shared__ double red[2][256][VEC];
     const int rpb = 256 / cpb;
     const int c = (blockIdx.x * cpb + threadIdx.x % cpb) * VEC;
@@ -265,11 +266,11 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
         for (int k = 1; k < rpb; ++k)
 #pragma unroll
             for (int r = 0; r < VEC; ++r) { s[r] += red[0][threadIdx.x + k * cpb][r]; q[r] += red[1][threadIdx.x + k * cpb][r]; }
-        float* row = part + (size_t)blockIdx.y * 2 * C;
+        double* row = part + (size_t)blockIdx.y * 2 * C;
 #pragma unroll
         for (int r = 0; r < VEC; ++r) {
-            row[c + r] = (float)s[r];
-            row[C + c + r] = (float)q[r];
+            row[c + r] = s[r];
+            row[C + c + r] = q[r];
         }
     }
 }
@@ -317,8 +318,9 @@ __global__ __launch_bounds__(256) void fold_partials_kernel(const float* __restr
 }
 
 // sums -> stats[0..C) = mean, stats[C..2C) = rstd; running buffers updated as nn.BatchNorm does (momentum 0.1,
-// unbiased variance for the running estimate)
-__global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ part, int P, float* __restrict__ stats,
+// unbiased variance for the running estimate).  PT: double rows from bn_stats_kernel, float rows from the GEMM's colstats epilogue
+template <typename PT>
+__global__ __launch_bounds__(1024) void bn_finalize_kernel(const PT* __restrict__ part, int P, float* __restrict__ stats,
                                                            float* __restrict__ running_mean, float* __restrict__ running_var,
                                                            int64_t* __restrict__ nbt, int M, int C, float eps, float momentum) {
     __shared__ double l[2][64][17];
@@ -328,8 +330,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
     if (c < C) {
         int p = lane;
         for (; p + 64 < P; p += 128) {
-            const float s0 = part[(size_t)p * 2 * C + c], q0 = part[(size_t)p * 2 * C + C + c];
-            const float s1 = part[(size_t)(p + 64) * 2 * C + c], q1 = part[(size_t)(p + 64) * 2 * C + C + c];
+            const PT s0 = part[(size_t)p * 2 * C + c], q0 = part[(size_t)p * 2 * C + C + c];
+            const PT s1 = part[(size_t)(p + 64) * 2 * C + c], q1 = part[(size_t)(p + 64) * 2 * C + C + c];
             s += (double)s0 + (double)s1;
             q += (double)q0 + (double)q1;
         }
@@ -365,7 +367,8 @@ __global__ __launch_bounds__(256) void bn_running_stats_kernel(const float* __re
 
 // synchronised BatchNorm, forward: partial rows -> sums[0..C) = sum y, sums[C..2C) = sum y^2, sums[2C] = M as doubles (the
 // all-reduce hook then adds the ranks up), and statistics from such sums
-__global__ __launch_bounds__(1024) void bn_sums_kernel(const float* __restrict__ part, int P, double* __restrict__ sums, int M, int C) {
+template <typename PT>
+__global__ __launch_bounds__(1024) void bn_sums_kernel(const PT* __restrict__ part, int P, double* __restrict__ sums, int M, int C) {
     __shared__ double l[2][64][17];
     const int col = threadIdx.x & 15, lane = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + col;
@@ -1010,17 +1013,19 @@ int eoe_bn_sync_allreduce(void* buf, int64_t count, int is_f64, void* stream) {
     return 0;
 }
 
-// partial rows [P][2C] -> stats (+ running buffers); with the hook: -> double sums behind the rows -> all-reduce -> stats
-static int bn_finalize_rows(const float* rows, int P, float* sums_scratch, float* stats, float* running_mean, float* running_var,
+// partial rows [P][2C] (PT = float or double) -> stats (+ running buffers); with the hook: -> double sums behind the rows -> all-reduce
+// -> stats
+template <typename PT>
+static int bn_finalize_rows(const PT* rows, int P, float* sums_scratch, float* stats, float* running_mean, float* running_var,
                             int64_t* nbt, int M, int C, float eps, float momentum, hipStream_t s) {
     if (!g_bn_sync_fn) {
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 16)), dim3(1024), 0, s, rows, P, stats, running_mean, running_var, nbt, M, C,
+        hipLaunchKernelGGL(bn_finalize_kernel<PT>, dim3(cdiv(C, 16)), dim3(1024), 0, s, rows, P, stats, running_mean, running_var, nbt, M, C,
                            eps, momentum);
         EOE_CHECK_LAUNCH("bn_finalize");
         return 0;
     }
     double* dsum = (double*)(sums_scratch + (size_t)EOE_BN_PARTIALS * 2 * C);        // the 3 spare rows of EOE_BN_SCRATCH: 3C doubles
-    hipLaunchKernelGGL(bn_sums_kernel, dim3(cdiv(C, 16)), dim3(1024), 0, s, rows, P, dsum, M, C);
+    hipLaunchKernelGGL(bn_sums_kernel<PT>, dim3(cdiv(C, 16)), dim3(1024), 0, s, rows, P, dsum, M, C);
     EOE_CHECK_LAUNCH("bn_sums");
     EOE_TRY(eoe_bn_sync_allreduce(dsum, 2 * (int64_t)C + 1, 1, (void*)s));
     hipLaunchKernelGGL(bn_finalize_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)dsum, stats, running_mean, running_var,
@@ -1051,10 +1056,13 @@ extern "C" int eoe_bn_stats(const float* y, float* sums_scratch, float* stats, f
     if (gy * gx > 1024) gy = 1024 / gx;
     if (gy > 512) gy = 512;
     if (gy < 1) gy = 1;
-    if (vec == 4) hipLaunchKernelGGL(bn_stats_kernel<4>, dim3(gx, gy), dim3(256), 0, s, y, sums_scratch, M, C, cpb);
-    else hipLaunchKernelGGL(bn_stats_kernel<1>, dim3(gx, gy), dim3(256), 0, s, y, sums_scratch, M, C, cpb);
+    // gy <= 512 rows of 2C doubles: the EOE_BN_PARTIALS rows of 2C floats of the scratch
+    EOE_CHECK_ARG(((uintptr_t)sums_scratch & 7) == 0, "bn_stats: sums_scratch must be 8-byte aligned");
+    double* part = (double*)sums_scratch;
+    if (vec == 4) hipLaunchKernelGGL(bn_stats_kernel<4>, dim3(gx, gy), dim3(256), 0, s, y, part, M, C, cpb);
+    else hipLaunchKernelGGL(bn_stats_kernel<1>, dim3(gx, gy), dim3(256), 0, s, y, part, M, C, cpb);
     EOE_CHECK_LAUNCH("bn_stats");
-    return bn_finalize_rows(sums_scratch, gy, sums_scratch, stats, running_mean, running_var, num_batches_tracked, M, C, eps, momentum, s);
+    return bn_finalize_rows((const double*)part, gy, sums_scratch, stats, running_mean, running_var, num_batches_tracked, M, C, eps, momentum, s);
 }
 
 extern "C" int eoe_bn_stats_partials(const float* part, int R, float* sums_scratch, float* stats, float* running_mean,

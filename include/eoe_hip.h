@@ -492,7 +492,8 @@ int eoe_stem_unpack_wgrad(const float* g, float* dw, int cout, int kh, int kw, v
 
 /* batch statistics of y fp32 [M,C]: stats[0..C) = mean, stats[C..2C) = 1/sqrt(var+eps) (biased var); training updates
  * running_mean/var (momentum, unbiased var) and num_batches_tracked as nn.BatchNorm does (cnn.py:57-66); eval reads
- * the running buffers.  sums_scratch: EOE_BN_SCRATCH(C) floats (per-workgroup partial sums: no atomics). */
+ * the running buffers.  sums_scratch: EOE_BN_SCRATCH(C) floats, 8-byte aligned (per-workgroup partial sums, kept in double by
+ * eoe_bn_stats: no atomics). */
 #define EOE_BN_PARTIALS 1024
 #define EOE_BN_SCRATCH(C) ((EOE_BN_PARTIALS + 3) * 2 * (C))
 /* Synchronised BatchNorm for data-parallel training (the reference is single-device: its BatchNorm sees the whole batch,
