@@ -228,6 +228,194 @@ extern "C" int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int W
     return eoe_crop_flip_u8_c(src, n_src, Hs, Ws, 3, params, out, n, Ho, Wo, flip_first, stream);
 }
 
+// ---- CLIP's per-sample upsample inside the chain (main/train_clip_cifar.py:26-35, train_clip_fmnist.py:27-36, train_clip_mnist.py:25-29):
+//   ... RandomCrop(S, padding) -> RandomHorizontalFlip -> Resize(P, BICUBIC) -> CenterCrop(P) -> convert("RGB") -> ToTensor -> noise -> Normalize
+// The resize comes after the random crop / flip, so it runs per sample per step.  A slot's source is only S x S x C bytes (3 KB at
+// 32 x 32 x 3), so the whole chain of a slot runs out of LDS and the only HBM traffic that matters is the fp32 store.  A workgroup
+// takes one BAND of R output rows of one slot (n * bands workgroups: 256 slots alone would leave most of the chip idle):
+//   1  gathers the few crop rows its band needs (rows [r0, r0 + nr), read off the vertical tap table) into LDS, by the crop / flip
+//      rules of eoe_crop_flip_u8_c, zero padding; loads are unconditional on clamped addresses, the padding is a select
+//   2  Pillow's horizontal pass on those rows, rounded to uint8 as Pillow rounds it, into LDS planes [C][nr][P]
+//   3  the vertical pass for 4 adjacent outputs of one row and plane per thread (one 4-byte LDS read per tap), the L -> RGB
+//      replication, then ToTensor / noise / Normalize in the statements of augment_kernel, one 16-byte store
+// Stages 1-3 up to the byte are integer arithmetic, the arithmetic of resize_pass_kernel below.  This kernel stands in front of
+// the `fp contract(off)` pragma further down on purpose: augment_kernel is compiled with contraction, and the fp32 of this kernel is
+// that of the composed chain bit for bit only under the same setting.
+namespace {
+
+constexpr int AR_PRECISION_BITS = 32 - 8 - 2;                            // Resample.c PRECISION_BITS (RESIZE_PRECISION_BITS below)
+
+__device__ __forceinline__ int ar_clip8(int ss) {
+    ss >>= AR_PRECISION_BITS;
+    return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+}
+
+// ToTensor, noise and Normalize of byte v at (c, y, x) of slot b of an [., 3, P, P] batch: augment_kernel's statements
+__device__ __forceinline__ float ar_to_float(int v, int c, int y, int x, int P, int b, const float* __restrict__ mean,
+                                             const float* __restrict__ stdv, float noise_std, unsigned long long seed) {
+    float a = (float)v / 255.0f;                                             // ToTensor
+    if (noise_std > 0.f) {
+        const unsigned long long e = ((unsigned long long)c * P + y) * P + x;
+        const unsigned long long z = splitmix64((seed << 40) + ((unsigned long long)b << 18) + e);
+        const float u1 = (float)((z >> 40) + 1ull) * (1.0f / 16777216.0f);          // (0, 1]
+        const float u2 = (float)((z >> 16) & 0xFFFFFFull) * (1.0f / 16777216.0f);   // [0, 1)
+        a += noise_std * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+    }
+    if (mean) a = (a - mean[c]) / stdv[c];
+    return a;
+}
+
+// C source channels, KS taps per output (3 bilinear, 5 bicubic: an upsample's support is the filter's own).  Dynamic LDS:
+// crop [nr_cap][S * C] (crop_bytes, a multiple of 16), then hbuf [C][nr_cap][Pp], Pp = P rounded up to 4.  Every index taken from
+// the tap tables is clamped to the buffers, so a wrong table gives wrong pixels, never an access outside them.
+template <int C, int KS>
+__global__ __launch_bounds__(256) void augment_resize_kernel(const uint8_t* __restrict__ src, long long n_src, const int32_t* __restrict__ params,
+                                                             const int32_t* __restrict__ bounds, const int32_t* __restrict__ kk,
+                                                             const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                             float* __restrict__ out, int Hs, int Ws, int S, int P, int bands, int R,
+                                                             int nr_cap, int crop_bytes, int flip_first, int vec, float noise_std,
+                                                             unsigned long long seed) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ar_lds[];
+    uint8_t* crop = ar_lds;
+    uint8_t* hbuf = ar_lds + crop_bytes;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / bands, band = blockIdx.x % bands;
+    const int y0 = band * R, y1 = min(y0 + R, P);                        // this band's output rows [y0, y1)
+    const int Pp = (P + 3) & ~3;
+    // the source rows the band's vertical taps reach: first row of its first output, past-the-last row of its last (both grow with y)
+    const int r0 = min(max(bounds[2 * y0], 0), S - 1);
+    const int rend = min(bounds[2 * (y1 - 1)] + bounds[2 * (y1 - 1) + 1], S);
+    const int nr = min(max(rend - r0, 1), nr_cap);
+
+    // 1: gather
+    const int idx = params[b * 4 + 0], top = params[b * 4 + 1], left = params[b * 4 + 2], flip = params[b * 4 + 3];
+    const bool in_set = idx >= 0 && (long long)idx < n_src;
+    const uint8_t* img = src + (size_t)(in_set ? idx : 0) * Hs * Ws * C;
+    for (int i = tid; i < nr * S; i += 256) {
+        const int r = i / S, x = i - r * S;
+        const long long sy = (long long)top + r0 + r;
+        long long sx;
+        if (flip_first) sx = flip ? (long long)Ws - 1 - ((long long)left + x) : (long long)left + x;    // flip the source, then crop
+        else sx = (long long)left + (flip ? S - 1 - x : x);                                             // crop, then flip the crop
+        const bool ok = in_set && sy >= 0 && sy < Hs && sx >= 0 && sx < Ws;
+        const int cy = (int)min(max(sy, 0ll), (long long)Hs - 1), cx = (int)min(max(sx, 0ll), (long long)Ws - 1);
+        const uint8_t* p = img + ((size_t)cy * Ws + cx) * C;
+        int v[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = p[c];
+#pragma unroll
+        for (int c = 0; c < C; ++c) crop[i * C + c] = (uint8_t)(ok ? v[c] : 0);                         // RandomCrop pads with 0
+    }
+    __syncthreads();
+
+    // 2: horizontal pass, a thread per output column: its taps stay in registers over the rows and channels
+    for (int x = tid; x < P; x += 256) {
+        const int xmin = min(max(bounds[2 * x], 0), S - 1);
+        const int cnt = min(max(bounds[2 * x + 1], 0), min(KS, S - xmin));
+        int k[KS], off[KS];
+#pragma unroll
+        for (int j = 0; j < KS; ++j) {
+            const int t = kk[x * KS + j];
+            k[j] = j < cnt ? t : 0;
+            off[j] = min(xmin + j, S - 1) * C;
+        }
+        for (int r = 0; r < nr; ++r) {
+            const uint8_t* row = crop + r * S * C;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int ss = 1 << (AR_PRECISION_BITS - 1);
+#pragma unroll
+                for (int j = 0; j < KS; ++j) ss += (int)row[off[j] + c] * k[j];
+                hbuf[(c * nr_cap + r) * Pp + x] = (uint8_t)ar_clip8(ss);
+            }
+        }
+    }
+    __syncthreads();
+
+    // 3: vertical pass and the fp32 tail; quads run along x first, so a wave stores 1 KiB of consecutive floats
+    const int Q = Pp / 4, rows = y1 - y0;
+    const int nq = 3 * rows * Q;
+    for (int q = tid; q < nq; q += 256) {
+        const int xq = q % Q, yy = (q / Q) % rows, co = q / (Q * rows);
+        const int cs = C == 3 ? co : 0;                                  // convert("RGB") of an L image: the byte, three times
+        const int y = y0 + yy, x0 = xq * 4;
+        const int ymin = min(max(bounds[2 * y], 0), S - 1);
+        const int cnt = min(max(bounds[2 * y + 1], 0), min(KS, S - ymin));
+        int ss[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ss[k] = 1 << (AR_PRECISION_BITS - 1);
+#pragma unroll
+        for (int j = 0; j < KS; ++j) {
+            const int t = kk[y * KS + j];
+            const int kj = j < cnt ? t : 0;
+            const int rr = min(max(ymin + j - r0, 0), nr - 1);
+            const unsigned w = *reinterpret_cast<const unsigned*>(hbuf + (cs * nr_cap + rr) * Pp + x0);
+            ss[0] += (int)(w & 255u) * kj; ss[1] += (int)((w >> 8) & 255u) * kj;
+            ss[2] += (int)((w >> 16) & 255u) * kj; ss[3] += (int)(w >> 24) * kj;
+        }
+        float a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = ar_to_float(ar_clip8(ss[k]), co, y, x0 + k, P, b, mean, stdv, noise_std, seed);
+        float* o = out + (((size_t)b * 3 + co) * P + y) * P + x0;
+        if (vec) *reinterpret_cast<float4*>(o) = make_float4(a[0], a[1], a[2], a[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < P) o[k] = a[k];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int eoe_augment_resize_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, int crop_h,
+                                        int crop_w, int n_px, int filter, const int32_t* bounds, const int32_t* kk, const float* mean,
+                                        const float* stdv, float* out, int n, int flip_first, float noise_std, uint64_t seed,
+                                        void* stream) {
+    EOE_CHECK_ARG(C == 1 || C == 3, "augment_resize_batch: C must be 1 or 3, not %d", C);
+    EOE_CHECK_ARG(src && params && bounds && kk && out && n_src > 0 && n > 0 && Hs > 0 && Ws > 0 && crop_h > 0 && crop_w > 0 && n_px > 0,
+                  "augment_resize_batch: bad args");
+    EOE_CHECK_ARG(filter == EOE_RESIZE_BILINEAR || filter == EOE_RESIZE_BICUBIC,
+                  "augment_resize_batch: filter must be EOE_RESIZE_BILINEAR or EOE_RESIZE_BICUBIC, not %d", filter);
+    EOE_CHECK_ARG(crop_h == crop_w, "augment_resize_batch: the crop must be square, not %d x %d (CenterCrop after Resize is the identity "
+                  "only then)", crop_h, crop_w);
+    EOE_CHECK_ARG(crop_h <= 64 && n_px <= 256, "augment_resize_batch: crop <= 64 and n_px <= 256 (a band's rows live in LDS), not %d -> %d",
+                  crop_h, n_px);
+    EOE_CHECK_ARG(n_px >= crop_h, "augment_resize_batch: %d -> %d is a downscale; only upsampling (n_px >= crop) is built", crop_h, n_px);
+    EOE_CHECK_ARG((mean == nullptr) == (stdv == nullptr), "augment_resize_batch: mean/std must both be given or both NULL");
+    EOE_CHECK_ARG(n < (1 << 22) && (size_t)3 * n_px * n_px < (1u << 18) && seed < (1ull << 24) && noise_std >= 0.f,
+                  "augment_resize_batch: n < 2^22, 3*n_px*n_px < 2^18, seed < 2^24 (the counter layout of the noise generator)");
+    const int S = crop_h, P = n_px;
+    const int support = filter == EOE_RESIZE_BILINEAR ? 1 : 2;          // not stretched: the scale is <= 1
+    // bands: about 2048 workgroups in flight where the batch allows it, and at least 8 output rows per band
+    int bands = (2048 + n - 1) / n;
+    if (bands > P / 8) bands = P / 8;
+    if (bands < 1) bands = 1;
+    const int R = (P + bands - 1) / bands;
+    bands = (P + R - 1) / R;
+    // R consecutive outputs have their centres within (R - 1) * S / P source rows; each end reaches `support` rows further
+    int nr_cap = (int)((long long)(R - 1) * S / P) + 2 * support + 2;
+    if (nr_cap > S) nr_cap = S;
+    const int Pp = (P + 3) & ~3;
+    const int crop_bytes = (nr_cap * S * C + 15) & ~15;
+    const size_t lds = (size_t)crop_bytes + (size_t)C * nr_cap * Pp;      // <= 12 KiB + 48 KiB at S = 64, P = 256, C = 3, one band
+    EOE_CHECK_ARG(lds <= 64 * 1024, "augment_resize_batch: %zu bytes of LDS", lds);
+    const int vec = P % 4 == 0 && (uintptr_t)out % 16 == 0;
+    ProfScope ps("augment_resize_batch", 0, (double)C * n * S * S + 4.0 * 3 * n * P * P, stream);
+    const dim3 grid((unsigned)((size_t)n * bands)), block(256);
+#define EOE_AR_LAUNCH(CC, KS)                                                                                                      \
+    hipLaunchKernelGGL((augment_resize_kernel<CC, KS>), grid, block, lds, (hipStream_t)stream, src, (long long)n_src, params, bounds, kk, \
+                       mean, stdv, out, Hs, Ws, S, P, bands, R, nr_cap, crop_bytes, flip_first, vec, noise_std, (unsigned long long)seed)
+    if (C == 3) {
+        if (support == 2) EOE_AR_LAUNCH(3, 5); else EOE_AR_LAUNCH(3, 3);
+    } else {
+        if (support == 2) EOE_AR_LAUNCH(1, 5); else EOE_AR_LAUNCH(1, 3);
+    }
+#undef EOE_AR_LAUNCH
+    EOE_CHECK_LAUNCH("augment_resize_batch");
+    return 0;
+}
+
 // Grayscale(1) (main/train_fmnist.py:32; torchvision hands it to Pillow's Image.convert("L"), libImaging/Convert.c rgb2l): uint8 NHWC
 // [., 3] -> [., 1], L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, byte for byte.  Deterministic and first in the chain, so a resident
 // set is converted once.  A thread takes 16 pixels: three 16-byte loads, one 16-byte store; the pixels past the last whole 16 (all of

@@ -269,6 +269,60 @@ def clip_preprocess(src_u8, n_px=224):
     return augment_batch(r, p, (n_px, n_px), CLIP_MEAN, CLIP_STD, True, 0.0, 0)
 
 
+_TAP_TABLES = {}             # (crop, n_px, filter, device) -> (bounds, kk) on that device: uploaded once, not per step
+
+
+def _cached_resize_tables(in_size, out_size, filt, device):
+    key = (int(in_size), int(out_size), int(filt), str(device))
+    if key not in _TAP_TABLES:
+        _TAP_TABLES[key] = _resize_tables(in_size, out_size, filt, device)[:2]
+    return _TAP_TABLES[key]
+
+
+def augment_resize_batch(src_u8, params, crop, n_px, mean=None, std=None, flip_first=True, noise_std=0.001, seed=0,
+                         interpolation="bicubic"):
+    """the tail of the reference's small-image CLIP chains (`main/train_clip_cifar.py:26-35`, `train_clip_fmnist.py:27-36`,
+    `train_clip_mnist.py:25-29`) in ONE kernel (`eoe_augment_resize_batch`): gather + RandomCrop(crop, zero padding) +
+    RandomHorizontalFlip, then 'clip_pil_preprocessing' (`training/clip.py:34-43`: Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
+    convert("RGB")), ToTensor, noise, Normalize.  The upsample follows the random crop, so it cannot be done once on the resident
+    set as `resize=` is; per slot the crop, Pillow's two uint8 passes and the L -> RGB replication run out of LDS, byte-exact with
+    `crop_flip_u8 -> resize_u8`, and only the fp32 batch is written.
+    src_u8 uint8 [n_src,Hs,Ws,C] (GPU), C = 1 or 3; params int32 [n,4] = (index, top, left, flip) (GPU); crop: the square crop's
+    side (<= 64); n_px >= crop (<= 256) -> fp32 NCHW [n,3,n_px,n_px]; mean / std hold three values, also for C = 1"""
+    from ._lib import check, lib, EOE_RESIZE_BILINEAR, EOE_RESIZE_BICUBIC
+    if not (src_u8.is_cuda and params.is_cuda):
+        raise RuntimeError("augment_resize_batch needs GPU tensors (there is no CPU fallback)")
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
+    ch = _channels(src_u8, "augment_resize_batch")
+    assert params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous()
+    if interpolation not in ("bilinear", "bicubic"):
+        raise ValueError(f"augment_resize_batch: interpolation must be 'bilinear' or 'bicubic', not {interpolation!r}")
+    filt = EOE_RESIZE_BILINEAR if interpolation == "bilinear" else EOE_RESIZE_BICUBIC
+    ch_crop, cw_crop = (crop, crop) if isinstance(crop, int) else (int(crop[0]), int(crop[1]))
+    n_px = int(n_px)
+    if ch_crop != cw_crop:
+        raise ValueError(f"augment_resize_batch: the crop must be square, not {ch_crop} x {cw_crop} (CenterCrop after Resize is the "
+                         "identity only for square crops)")
+    if not 0 < ch_crop <= n_px:
+        raise ValueError(f"augment_resize_batch: {ch_crop} -> {n_px} is not an upsample (only n_px >= crop is built)")
+    n, dev = params.shape[0], src_u8.device
+    m = torch.as_tensor(mean, dtype=torch.float32, device=dev).contiguous() if mean is not None else None
+    s = torch.as_tensor(std, dtype=torch.float32, device=dev).contiguous() if std is not None else None
+    for name, t in (("mean", m), ("std", s)):
+        if t is not None and t.numel() != 3:
+            raise ValueError(f"augment_resize_batch: {name} must hold three values (the batch is RGB), not {t.numel()}")
+    out = torch.empty((n, 3, n_px, n_px), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    bounds, kk = _cached_resize_tables(ch_crop, n_px, filt, dev)
+    check(lib.eoe_augment_resize_batch(src_u8.data_ptr(), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], ch, params.data_ptr(),
+                                       ch_crop, cw_crop, n_px, filt, bounds.data_ptr(), kk.data_ptr(),
+                                       None if m is None else m.data_ptr(), None if s is None else s.data_ptr(), out.data_ptr(), n,
+                                       1 if flip_first else 0, float(noise_std), int(seed), torch.cuda.current_stream().cuda_stream),
+          "eoe_augment_resize_batch")
+    return out
+
+
 def gray_set(images_u8, device):
     """a resident set under `Grayscale(1)`: `[n, H, W]` is taken as `[n, H, W, 1]`, a 3-channel set is converted once on the
     device (`grayscale_u8`), a 1-channel set passes through (Grayscale(1) of an `L` image is the identity)"""
@@ -305,16 +359,43 @@ class ResidentImageSource:
 
     `flip=False` leaves RandomHorizontalFlip out (`main/train_mnist.py`: no flip, no crop, no noise): the flip bits are zeros and
     NO flip draw is made, as an empty `Compose` draws nothing -- the generator then yields other crop origins in later steps than
-    with `flip=True`, whose draw order is what it always was."""
+    with `flip=True`, whose draw order is what it always was.
+
+    `clip_preprocessing=n_px` puts CLIP's own transform where the reference's small-image CLIP runners have it
+    (`main/train_clip_cifar.py:26-35`, `train_clip_fmnist.py:27-36`, `train_clip_mnist.py:25-29`): after RandomCrop / flip and before
+    ToTensor, 'clip_pil_preprocessing' = Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> convert("RGB") (`training/clip.py:34-43`), and
+    Normalize with CLIP's mean / std (the defaults then; `mean` / `std` take three values, also under `grayscale=True`).  The
+    upsample follows the random crop, so it runs per sample per step: each half is one `augment_resize_batch` launch in place of
+    `augment_batch`; draws and draw order are unchanged, ColorJitter still comes first.  Batches are `[., 3, n_px, n_px]`.  Test
+    batches get CLIP's transform alone on the raw test images (`val_transform` is empty, `training/clip.py:44-46`), which must be
+    square, and are built one at a time while the loader is iterated.  Where the stage is the identity -- a 3-channel set whose
+    crop (test images: whose size) is n_px already -- the path without the option runs, bit for bit.  Only square crops of at
+    most 64 px and upsampling to at most 256 px are built; `normalize=` / `ds_statistics=` (statistics fitted on the set) and a
+    pre-tensor sharpen MSM are refused with it."""
 
     nominal_label, anomalous_label = 0, 1
 
     def __init__(self, normal_u8, oe_u8, test_u8, test_labels, crop, padding=0, mean=None, std=None, flip_first=True,
                  noise_std=0.001, seed=0, device="cuda", resize=None, test_resize=None, color_jitter=None, interpolation="bilinear",
-                 normal_index=None, normalize=None, ds_statistics=None, grayscale=False, flip=True):
+                 normal_index=None, normalize=None, ds_statistics=None, grayscale=False, flip=True, clip_preprocessing=None):
         """resize / test_resize: `transforms.Resize` argument applied once to the resident train / test sets (None: as given);
-        color_jitter: (brightness, contrast, saturation, hue) of `transforms.ColorJitter`, drawn per sample per step"""
+        color_jitter: (brightness, contrast, saturation, hue) of `transforms.ColorJitter`, drawn per sample per step;
+        clip_preprocessing: n_px of CLIP's transform inside the chain (the class docstring)"""
         dev = torch.device(device)
+        if clip_preprocessing is not None:
+            if normalize is not None or ds_statistics is not None:
+                raise ValueError("clip_preprocessing normalises with CLIP's own (or the given three-valued) mean / std, as "
+                                 "'clip_tensor_preprocessing' does; it cannot be combined with normalize= / ds_statistics=")
+            if not isinstance(crop, int):
+                if len(crop) != 2 or int(crop[0]) != int(crop[1]):
+                    raise ValueError(f"clip_preprocessing needs a square crop, not {tuple(crop)}: CenterCrop(n_px) after "
+                                     "Resize(n_px) is the identity only then")
+                crop = int(crop[0])
+            if not 0 < crop <= int(clip_preprocessing):
+                raise NotImplementedError(f"clip_preprocessing={clip_preprocessing} on a crop of {crop}: only upsampling "
+                                          "(n_px >= crop) is built")
+            if mean is None and std is None:
+                mean, std = CLIP_MEAN, CLIP_STD
         if grayscale and color_jitter is not None:
             raise ValueError("color_jitter works on RGB images and cannot be combined with grayscale=True (no chain of the "
                              "reference has both)")
@@ -331,6 +412,16 @@ class ResidentImageSource:
         self.test_y = test_labels.clone()
         self.crop, self.padding, self.mean, self.std = int(crop), int(padding), mean, std
         self.flip_first, self.noise_std, self.seed = flip_first, noise_std, int(seed)
+        self.clip_preprocessing = None if clip_preprocessing is None else int(clip_preprocessing)
+        if self.clip_preprocessing is not None:
+            th, tw, px = self.test.shape[1], self.test.shape[2], self.clip_preprocessing
+            if th != tw:
+                raise ValueError(f"clip_preprocessing needs square test images, not {th} x {tw}: Resize(n_px) of another shape is "
+                                 "not n_px x n_px and CenterCrop would cut it")
+            for what, side, chans in (("crop", self.crop, self.normal.shape[3]), ("test images", th, self.test.shape[3])):
+                if self._clip_px(side, chans) is not None and not (side <= px and side <= 64 and px <= 256):
+                    raise NotImplementedError(f"clip_preprocessing={px} on {what} of {side} px: only upsampling from at most 64 px to "
+                                              "at most 256 px is built")
         self.normalize = None
         self.ds_statistics = None
         self.normal_index = None if normal_index is None else torch.as_tensor(normal_index, dtype=torch.int64).clone()
@@ -397,11 +488,23 @@ class ResidentImageSource:
         claimed MSMs, which the trainer then leaves out of the step batch's apply_msms; test batches (centre crops, no noise)
         stay with apply_msms."""
         self._pre_msms = [m for m in msms if m.transform_str == "sharpen" and m.ds_part_str in ("train_nominal", "train_oe")]
+        if self._pre_msms and self._clip_px(self.crop, self.normal.shape[3]) is not None:
+            self._pre_msms = []
+            raise NotImplementedError("a train sharpen MSM works on the uint8 crop in front of clip_preprocessing's upsample; that "
+                                      "combination is not built")
         return list(self._pre_msms)
+
+    def _clip_px(self, side, channels):
+        """n_px where clip_preprocessing has work to do on square uint8 images of this side (train: the crop, test: the image) and
+        channel count; None where the option is off or the stage is the identity: 3 channels, n_px wide already"""
+        px = self.clip_preprocessing
+        return None if px is None or (side == px and channels == 3) else px
 
     def _augment_half(self, src, p, nominal, mean, std, seed):
         """one half of a step batch: augment_batch, or with claimed sharpen MSMs for this half the reference's order"""
         ops = [m for m in getattr(self, "_pre_msms", ()) if (m.ds_part_str == "train_nominal") == nominal]
+        if self._clip_px(self.crop, src.shape[3]) is not None:               # a sharpen MSM is refused together with it (pre_tensor_msms)
+            return augment_resize_batch(src, p, self.crop, self.clip_preprocessing, mean, std, self.flip_first, self.noise_std, seed)
         if not ops or p.shape[0] == 0:
             return augment_batch(src, p, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, seed)
         from .msm import sharpen_percent, sharpen_u8
@@ -468,6 +571,23 @@ class ResidentImageSource:
                 n = outer.normal.shape[0] if outer.normal_index is None else len(outer.normal_index)
                 return math.ceil(n / batch_size)
 
+        if self._clip_px(self.test.shape[1], self.test.shape[3]) is not None:
+            # CLIP's transform on the raw test images (val_transform is empty, training/clip.py:44-46): the same kernel with an
+            # identity "crop" of the whole image, no noise; 224 x 224 x 3 floats per image, so a batch exists only while it is used
+            class _Test:
+                def __iter__(s):
+                    for lo in range(0, len(outer.test_y), batch_size):
+                        idx = torch.arange(lo, min(lo + batch_size, len(outer.test_y)))
+                        p = torch.zeros((len(idx), 4), dtype=torch.int32)
+                        p[:, 0] = idx
+                        x = augment_resize_batch(outer.test, p.to(outer.test.device), outer.test.shape[1], outer.clip_preprocessing,
+                                                 *outer._norm_args(), True, 0.0, 0)
+                        yield x, outer.test_y[idx], idx
+
+                def __len__(s):
+                    return math.ceil(len(outer.test_y) / batch_size)
+
+            return _Train(), _Test()
         # test split: centre crop, no flip, no noise (val_transform: ToTensor + normalize, train_cifar.py:39-42)
         Hs, Ws = self.test.shape[1], self.test.shape[2]
         test = []

@@ -887,6 +887,22 @@ int eoe_augment_batch_c(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C
 int eoe_crop_flip_u8_c(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, uint8_t* out, int n, int Ho,
                        int Wo, int flip_first, void* stream);
 int eoe_grayscale_u8(const uint8_t* src, uint8_t* dst, int64_t n_pixels, void* stream);
+/* CLIP's own preprocessing INSIDE the train chain (main/train_clip_cifar.py:26-35, train_clip_fmnist.py:27-36, train_clip_mnist.py:25-29):
+ *   RandomCrop(S, padding) / RandomHorizontalFlip -> Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> convert("RGB") -> ToTensor -> noise
+ *   -> Normalize.  The upsample follows the random crop, so it runs per sample per step: one launch does the whole chain.
+ *   eoe_augment_resize_batch  src uint8 [n_src, Hs, Ws, C] (C = 1 or 3), params as eoe_augment_batch -> out fp32 NCHW [n, 3, n_px, n_px]:
+ *       the crop_h x crop_w crop of eoe_crop_flip_u8_c (zero padding, both flip orders; a slot whose index lies outside
+ *       [0, n_src) is all padding), Pillow's horizontal then vertical pass crop -> n_px on uint8 (the arithmetic of
+ *       eoe_resize_pass_u8; the horizontal result is rounded to uint8 first), the byte repeated to three channels when C = 1, then
+ *       out = ((v / 255 + noise_std * N(0,1)) - mean[c]) / std[c] with the noise rule of eoe_augment_batch on element
+ *       e = (c*n_px + y)*n_px + x; mean / std hold 3 floats (or both NULL).
+ *       bounds / kk: the DEVICE copies of eoe_resize_coeffs(crop, n_px, filter) with ksize_cap = its ksize (3 bilinear, 5 bicubic);
+ *       the caller uploads them once per (crop, n_px, filter) and keeps them.
+ *       EOE_ERR_ARG before any launch: crop_h != crop_w (CenterCrop is then no identity), crop > 64, n_px > 256, n_px < crop
+ *       (downscaling), a filter other than EOE_RESIZE_BILINEAR / EOE_RESIZE_BICUBIC, 3*n_px*n_px >= 2^18, n >= 2^22, seed >= 2^24. */
+int eoe_augment_resize_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, int crop_h, int crop_w,
+                             int n_px, int filter, const int32_t* bounds, const int32_t* kk, const float* mean, const float* std,
+                             float* out, int n, int flip_first, float noise_std, uint64_t seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
