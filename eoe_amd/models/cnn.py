@@ -48,7 +48,8 @@ class CNN32(nn.Module):
     def _layer(self, x, conv, bn, is_image, flat_out):
         mean, std = self.normalize if (is_image and self.normalize is not None) else (None, None)
         # 5x5 stride 1 pad 2, LeakyReLU(0.01), MaxPool 2; a 16-bit copy of the output feeds the next conv's implicit GEMM
-        cfg = (self.training, bn.eps, bn.momentum, 2, is_image, mean, std, flat_out, (5, 5, 1, 2), 0.01, not flat_out)
+        cfg = ops.ConvUnit(training=self.training, eps=bn.eps, momentum=bn.momentum, pool=2, is_image=is_image, mean=mean, std=std,
+                           flat_out=flat_out, kernel=(5, 5, 1, 2), slope=0.01, want16=not flat_out)
         return ops.conv_bn_act_pool(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                     bn.num_batches_tracked, cfg)
 

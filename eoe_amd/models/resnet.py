@@ -27,7 +27,8 @@ def _conv_bn(x, conv, bn, training, slope, is_image=False, normalize=None, want1
     16-bit copy alone -- the fp32 tensor is not written)"""
     mean, std = normalize if (is_image and normalize is not None) else (None, None)
     k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-    cfg = (training, bn.eps, bn.momentum, pool, is_image, mean, std, False, (k, k, s, p), slope, want16, passthrough, only16)
+    cfg = ops.ConvUnit(training=training, eps=bn.eps, momentum=bn.momentum, pool=pool, is_image=is_image, mean=mean, std=std,
+                       flat_out=False, kernel=(k, k, s, p), slope=slope, want16=want16, passthrough=passthrough, only16=only16)
     return ops.conv_bn_act_pool(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                 bn.num_batches_tracked, cfg)
 

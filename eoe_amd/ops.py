@@ -8,7 +8,8 @@ import ctypes as C
 import math
 import os
 import weakref
-from typing import Optional
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1218,25 +1219,134 @@ def _f32_colsum(x2d: torch.Tensor, out: torch.Tensor):
     check(lib.eoe_cast_colsum(_p(x2d), _p(dummy), _p(out), _p(part), rows, cols, _lib.EOE_F16, 0, _stream()), "eoe_cast_colsum")
 
 
+class ConvUnit(NamedTuple):
+    """Configuration of one conv (+ bias) -> BatchNorm2d -> activation -> pool unit (`conv_bn_act_pool`), in the order of the positional tuple
+    it replaced: such a tuple of 8 to 13 entries converts with `ConvUnit(*t)`.  The defaults are CNN32's layer (`cnn.py:73-82`)."""
+    training: bool                  # BatchNorm normalises with the batch statistics and updates its running buffers; False: running statistics
+    eps: float                      # BatchNorm's eps ...
+    momentum: float                 # ... and momentum
+    pool: object                    # p: MaxPool2d(p) behind the activation (1 = none); (k, stride, pad): an overlapping MaxPool2d (resnet.py:96)
+    is_image: bool                  # the input is the fp32 NCHW image batch (first layer), not an fp32 NHWC activation
+    mean: Optional[torch.Tensor]    # with is_image: the per-channel Normalize fused into the first layer's gather (None = none) ...
+    std: Optional[torch.Tensor]     # ... plain tensors, not tracked by autograd
+    flat_out: bool                  # the output in the reference's NCHW-flattened order [n, cout*Ho*Wo] (`cnn.py:83`) instead of NHWC
+    kernel: tuple = (5, 5, 1, 2)    # (kh, kw, stride, pad) of the convolution
+    slope: float = 0.01             # the activation's negative slope: 0.01 = LeakyReLU, 0 = ReLU, 1 = none (`resnet.py:93-95,133-141`)
+    want16: bool = False            # also emit a 16-bit copy of the output (returned second, non-differentiable) for a following convolution
+    passthrough: bool = False       # also return the input itself (last output).  A residual block hands THAT to its junction as the shortcut,
+    #                                 so the junction's gradient for the shortcut arrives in this unit's backward (d_pass) and the dgrad GEMM
+    #                                 accumulates onto it -- instead of autograd adding the two gradients of the block input in a separate pass
+    only16: bool = False            # with want16: the output feeds ONE consumer that reads the 16-bit copy only (a BasicBlock's conv1 -> bn1 -> relu
+    #                                 -> conv2): the fp32 tensor is allocated for autograd's bookkeeping but never written (4 of 10 bytes per element)
+
+
+# what a BatchNorm unit's backward needs of its forward: the BatchNorm input [n, H, W, cout], what follows it, and the convolution in front of it
+# (input [n, Hi, Wi, cin]); the defaults: no convolution (BatchNorm1d)
+_ConvShape = namedtuple("_ConvShape", "n H W cout pool flat_out training slope cin is_image Hi Wi kh kw stride pad",
+                        defaults=(0, False, 1, 1, 1, 1, 1, 0))
+
+
+def _conv_shape(x, conv_w, cfg):
+    """the `_ConvShape` of the unit `cfg` with the weight conv_w [cout, cin, kh, kw] on x (NCHW if cfg.is_image, else NHWC)"""
+    kh, kw, stride, pad = cfg.kernel
+    n, Hi, Wi = (x.shape[0], x.shape[2], x.shape[3]) if cfg.is_image else x.shape[:3]
+    H, W = (Hi + 2 * pad - kh) // stride + 1, (Wi + 2 * pad - kw) // stride + 1       # conv output grid
+    return _ConvShape(n, H, W, conv_w.shape[0], cfg.pool, cfg.flat_out, cfg.training, float(cfg.slope), conv_w.shape[1], cfg.is_image,
+                      Hi, Wi, kh, kw, stride, pad)
+
+
+def _bn_act_pool_fwd(y, part, R, bn_w, bn_b, rm, rv, nbt, eps, momentum, s, ycode, dt16=None, only16=False):
+    """The tail of every BatchNorm unit: the statistics of y [n*H*W, cout] -- from the partial rows `part` [R][2][cout] a conv GEMM's epilogue
+    left, else with a pass over y -- then BatchNorm + activation + pool in one kernel.  Returns (out, out16, idx, stats).
+      ycode   the compute dtype's code, with EOE_Y16 where the fast path's GEMM wrote y in 16 bits (the fp32 paths never do)
+      dt16    the dtype of the 16-bit copy of the output to emit as well (fast path only: parity mode rounds no activation)
+      only16  `ConvUnit.only16`; it holds where that copy exists and has the output's own layout (non-overlapping pool, NHWC)"""
+    n, H, W, C, pool, dev = s.n, s.H, s.W, s.cout, s.pool, y.device
+    stats = torch.empty(2 * C, dtype=torch.float32, device=dev)
+    sums = scratch("bn_sums", (BN_SCRATCH * C,), torch.float32, dev)
+    if part is not None:
+        check(lib.eoe_bn_stats_partials(_p(part), R, _p(sums), _p(stats), _p(rm), _p(rv), _p(nbt), n * H * W, C, float(eps),
+                                        float(momentum), _stream()), "eoe_bn_stats_partials")
+    else:
+        check(lib.eoe_bn_stats(_p(y), _p(sums), _p(stats), _p(rm), _p(rv), _p(nbt), n * H * W, C, float(eps), float(momentum),
+                               1 if s.training else 0, _stream()), "eoe_bn_stats")
+    idx = None
+    if isinstance(pool, tuple):
+        # overlapping MaxPool2d(k, s, p) fused behind BN + act: the pre-pool activation is never written (resnet.py:93-96)
+        pk, pstride, ppad = pool
+        Ho, Wo = (H + 2 * ppad - pk) // pstride + 1, (W + 2 * ppad - pk) // pstride + 1
+        out = torch.empty((n, Ho, Wo, C), dtype=torch.float32, device=dev)
+        out16 = torch.empty((n, Ho, Wo, C), dtype=dt16, device=dev) if dt16 is not None else None
+        idx = torch.empty((n, Ho, Wo, C), dtype=torch.uint8, device=dev)
+        check(lib.eoe_bn_act_maxpool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out), _p(out16), _p(idx), n, H, W, C, pk,
+                                         pstride, ppad, s.slope, ycode, _stream()), "eoe_bn_act_maxpool_fwd")
+    else:
+        Ho, Wo = H // pool, W // pool
+        out = torch.empty((n, C * Ho * Wo) if s.flat_out else (n, Ho, Wo, C), dtype=torch.float32, device=dev)
+        out16 = torch.empty((n, Ho, Wo, C), dtype=dt16, device=dev) if (dt16 is not None and not s.flat_out) else None
+        dst, dst16, flat, out_f32 = out, out16, 1 if s.flat_out else 0, 1
+        if only16 and out16 is not None:
+            dst, dst16, flat, out_f32 = out16, None, 0, 0          # the kernel's 16-bit `out` form: `out` itself stays unwritten ...
+            out._eoe_unwritten = True                              # ... and says so to a consumer that cannot use the copy
+        check(lib.eoe_bn_act_pool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dst), _p(dst16), n, H, W, C, pool, flat, out_f32,
+                                      s.slope, ycode, _stream()), "eoe_bn_act_pool_fwd")
+    return out, out16, idx, stats
+
+
+def _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, dy_dtype, dy_f32, code, maxpool_code=None):
+    """Backward of `_bn_act_pool_fwd`: dout (layout of `out`) -> (dy [n*H*W, cout], dgamma, dbeta).
+      dy_dtype, dy_f32   dy is the operand of what comes next: the fast path's 16-bit wgrad / dgrad GEMMs (compute dtype, 0), the fp32
+                         kernels of parity mode and the fp32 linear layer in front of a BatchNorm1d (float32, 1)
+      code               as `ycode` of the forward (EOE_Y16 where the saved y is 16-bit)
+      maxpool_code       if not `code`: eoe_bn_act_maxpool_bwd has no dy_f32 argument, it writes an fp32 dy when its code is EOE_F32"""
+    n, H, W, C, pool, dev = s.n, s.H, s.W, s.cout, s.pool, y.device
+    dout = dout.contiguous().float()
+    dy = torch.empty((n * H * W, C), dtype=dy_dtype, device=dev)
+    dg = _grad_target(bn_w) if bn_w is not None else None
+    db = _grad_target(bn_b) if bn_b is not None else None
+    red = scratch("bn_red", (BN_SCRATCH * C,), torch.float32, dev)
+    if isinstance(pool, tuple):
+        check(lib.eoe_bn_act_maxpool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(idx), _p(red), _p(dy), _p(dg), _p(db),
+                                         n, H, W, C, pool[0], pool[1], pool[2], 1 if s.training else 0, s.slope,
+                                         code if maxpool_code is None else maxpool_code, _stream()), "eoe_bn_act_maxpool_bwd")
+    else:
+        check(lib.eoe_bn_act_pool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(red), _p(dy), dy_f32, _p(dg), _p(db), n, H,
+                                      W, C, pool, 1 if s.flat_out else 0, 1 if s.training else 0, 0, s.slope, code, _stream()),
+              "eoe_bn_act_pool_bwd")
+    return dy, dg, db
+
+
+def _accumulates(d_pass, s) -> bool:
+    """the dgrad may write dx += onto the pass-through gradient itself: it is an fp32 tensor of dx's own layout"""
+    return d_pass is not None and d_pass.dtype == torch.float32 and d_pass.is_contiguous() and d_pass.shape == (s.n, s.Hi, s.Wi, s.cin)
+
+
+def _with_passthrough(body):
+    """backward of a conv unit around its pass-through input (`ConvUnit.passthrough`), whose gradient d_pass arrives last:
+    `body(ctx, dout, d_pass)` returns (dx, dw, dcb, dg, db, d_pass), d_pass = None once its dgrad has accumulated onto it"""
+    def backward(ctx, dout, *more):
+        d_pass = more[-1] if (ctx.passthrough and more) else None
+        if dout is None:                         # only the pass-through output was used downstream
+            return (d_pass,) + (None,) * 8
+        dx, dw, dcb, dg, db, d_pass = body(ctx, dout, d_pass)
+        if d_pass is not None:
+            dx = d_pass if dx is None else dx.add_(d_pass)
+        return dx, dw, dcb, dg, db, None, None, None, None
+    return backward
+
+
 class ConvBnActPoolParityFunction(torch.autograd.Function):
     """ConvBnActPoolFunction with the convolution in fp32 (parity mode); BatchNorm / activation / pooling are the same fp32
-    kernels as on the fast path.  Same cfg tuple; never emits 16-bit copies."""
+    kernels as on the fast path.  Same `ConvUnit`; never emits 16-bit copies (want16 and only16 do nothing here)."""
 
     @staticmethod
     def forward(ctx, x, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, cfg):
         _chk(x, conv_w, conv_b, bn_w, bn_b, rm, rv)
-        training, eps, momentum, pool, is_image, mean, std, flat_out = cfg[:8]
-        kh, kw, stride, pad = cfg[8] if len(cfg) > 8 else (5, 5, 1, 2)
-        slope = float(cfg[9]) if len(cfg) > 9 else 0.01
-        passthrough = bool(cfg[11]) if len(cfg) > 11 else False
+        mean, std = cfg.mean, cfg.std
         x_in = x
         x = x.contiguous().float()
-        cout, cin = conv_w.shape[0], conv_w.shape[1]
-        if is_image:
-            n, _, Hi, Wi = x.shape
-        else:
-            n, Hi, Wi, _ = x.shape
-        H, W = (Hi + 2 * pad - kh) // stride + 1, (Wi + 2 * pad - kw) // stride + 1
+        s = _conv_shape(x, conv_w, cfg)
+        n, H, W, cin, cout, is_image, Hi, Wi, kh, kw, stride, pad = s.n, s.H, s.W, s.cin, s.cout, s.is_image, s.Hi, s.Wi, s.kh, s.kw, s.stride, s.pad
         M, dev = n * H * W, x.device
         geo = _geo(n, Hi, Wi, cin, kh, kw, stride, pad, H, W)
         w = conv_w.contiguous()
@@ -1267,61 +1377,27 @@ class ConvBnActPoolParityFunction(torch.autograd.Function):
                 xq, wq, wkf = _round_mantissa(x, PARITY_EMULATE_BITS), _round_mantissa(w, PARITY_EMULATE_BITS), None      # (the kernel then reads the unpacked weights)
             check(lib.eoe_conv_f32_fwd(_p(xq), 1 if is_image else 0, _p(mean) if is_image else None, _p(std) if is_image else None, _p(wq),
                                        _p(conv_b), _p(y), geo, cout, _p(ws), PARITY_SPLITK_BYTES, _p(wkf), _stream()), "eoe_conv_f32_fwd")
-        stats = torch.empty(2 * cout, dtype=torch.float32, device=dev)
-        sums = scratch("bn_sums", (BN_SCRATCH * cout,), torch.float32, dev)
-        check(lib.eoe_bn_stats(_p(y), _p(sums), _p(stats), _p(rm), _p(rv), _p(nbt), M, cout, float(eps), float(momentum),
-                               1 if training else 0, _stream()), "eoe_bn_stats")
-        idx = None
-        code = dtype_code(_compute_dtype)
-        if isinstance(pool, tuple):
-            pk, pstride, ppad = pool
-            Ho, Wo = (H + 2 * ppad - pk) // pstride + 1, (W + 2 * ppad - pk) // pstride + 1
-            out = torch.empty((n, Ho, Wo, cout), dtype=torch.float32, device=dev)
-            idx = torch.empty((n, Ho, Wo, cout), dtype=torch.uint8, device=dev)
-            check(lib.eoe_bn_act_maxpool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out), None, _p(idx), n, H, W, cout, pk,
-                                             pstride, ppad, slope, code, _stream()), "eoe_bn_act_maxpool_fwd")
-        else:
-            Ho, Wo = H // pool, W // pool
-            out = torch.empty((n, cout * Ho * Wo) if flat_out else (n, Ho, Wo, cout), dtype=torch.float32, device=dev)
-            check(lib.eoe_bn_act_pool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out), None, n, H, W, cout, pool,
-                                          1 if flat_out else 0, 1, slope, code, _stream()), "eoe_bn_act_pool_fwd")
+        out, _, idx, stats = _bn_act_pool_fwd(y, None, 0, bn_w, bn_b, rm, rv, nbt, cfg.eps, cfg.momentum, s, dtype_code(_compute_dtype))
         ctx.save_for_backward(x, y, stats, conv_w, conv_b, bn_w, bn_b, idx, mean if is_image else None, std if is_image else None)
-        ctx.cfg = (n, H, W, cin, cout, pool, flat_out, training, is_image, Hi, Wi, kh, kw, stride, pad, slope)
-        ctx.packed = packed
-        ctx.passthrough = passthrough
-        if not passthrough:
+        ctx.shape, ctx.packed, ctx.passthrough = s, packed, bool(cfg.passthrough)
+        if not ctx.passthrough:
             return out
         ctx.set_materialize_grads(False)
         return out, x_in
 
     @staticmethod
-    def backward(ctx, dout, *more):
-        d_pass = more[-1] if (ctx.passthrough and more) else None
-        if dout is None:
-            return (d_pass,) + (None,) * 8
+    @_with_passthrough
+    def backward(ctx, dout, d_pass):
         x, y, stats, conv_w, conv_b, bn_w, bn_b, idx, mean, std = ctx.saved_tensors
-        n, H, W, cin, cout, pool, flat_out, training, is_image, Hi, Wi, kh, kw, stride, pad, slope = ctx.cfg
-        packed = getattr(ctx, "packed", False)
+        s = ctx.shape
+        n, H, W, cin, cout, is_image, Hi, Wi, kh, kw, stride, pad = s.n, s.H, s.W, s.cin, s.cout, s.is_image, s.Hi, s.Wi, s.kh, s.kw, s.stride, s.pad
         dev = y.device
-        M = n * H * W
-        dout = dout.contiguous().float()
-        dy = torch.empty((M, cout), dtype=torch.float32, device=dev)
-        dg = _grad_target(bn_w) if bn_w is not None else None
-        db = _grad_target(bn_b) if bn_b is not None else None
-        red = scratch("bn_red", (BN_SCRATCH * cout,), torch.float32, dev)
-        if isinstance(pool, tuple):
-            check(lib.eoe_bn_act_maxpool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(idx), _p(red), _p(dy), _p(dg), _p(db),
-                                             n, H, W, cout, pool[0], pool[1], pool[2], 1 if training else 0, slope, _lib.EOE_F32, _stream()),
-                  "eoe_bn_act_maxpool_bwd")
-        else:
-            check(lib.eoe_bn_act_pool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(red), _p(dy), 1, _p(dg), _p(db), n, H,
-                                          W, cout, pool, 1 if flat_out else 0, 1 if training else 0, 0, slope,
-                                          dtype_code(_compute_dtype), _stream()), "eoe_bn_act_pool_bwd")
+        dy, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, torch.float32, 1, dtype_code(_compute_dtype), maxpool_code=_lib.EOE_F32)
         geo = _geo(n, Hi, Wi, cin, kh, kw, stride, pad, H, W)
         w = conv_w.contiguous()
         dw = _grad_target(conv_w)
         _side_ctx = _conv_wgrad_side_begin(dy, x) if CONV_ASYNC_WGRAD else None      # (see _conv_wgrad_side_begin: under dgrad + the next layer)
-        if packed:                                   # x = the NHWC4 image saved by forward: gradient of the zero-padded [cout, 4, kh, kw] weight
+        if ctx.packed:                               # x = the NHWC4 image saved by forward: gradient of the zero-padded [cout, 4, kh, kw] weight
             geo4 = _geo(n, Hi, Wi, 4, kh, kw, stride, pad, H, W)
             ws_bytes = int(lib.eoe_conv_f32_wgrad_workspace(geo4, cout))
             ws = scratch("parity_wgrad_ws", (ws_bytes // 4,), torch.float32, dev)
@@ -1341,17 +1417,14 @@ class ConvBnActPoolParityFunction(torch.autograd.Function):
             _f32_colsum(dy, dcb)
         dx = None
         if ctx.needs_input_grad[0] and not is_image:
-            acc = (d_pass is not None and d_pass.dtype == torch.float32 and d_pass.is_contiguous()
-                   and d_pass.shape == (n, Hi, Wi, cin))
+            acc = _accumulates(d_pass, s)
             dx = d_pass if acc else torch.empty((n, Hi, Wi, cin), dtype=torch.float32, device=dev)
             wkd = _parity_packed(conv_w, "d") if cin % 4 == 0 else None
             check(lib.eoe_conv_f32_dgrad(_p(dy), _p(w), _p(dx), geo, cout, 1 if acc else 0, _p(_parity_splitk_ws(dev)), PARITY_SPLITK_BYTES,
                                          _p(wkd), _stream()), "eoe_conv_f32_dgrad")
             if acc:
                 d_pass = None
-        if d_pass is not None:
-            dx = d_pass if dx is None else dx.add_(d_pass)
-        return dx, dw, dcb, dg, db, None, None, None, None
+        return dx, dw, dcb, dg, db, d_pass
 
 
 PARITY_SPLITK_BYTES = 16 << 20
@@ -1434,10 +1507,7 @@ CONV_Y16 = os.environ.get("EOE_CONV_Y16", "0") != "0"
 
 
 class ConvBnActPoolFunction(torch.autograd.Function):
-    """conv (+ bias) -> BatchNorm2d -> act -> MaxPool(pool), one layer per call: conv5x5(pad 2) + LeakyReLU(0.01) + pool 2
-    for `cnn.py:73-82` (the default when cfg has 8 entries); cfg[8] = (kh, kw, stride, pad) and cfg[9] = the activation's
-    negative slope (0 = ReLU, 1 = none) give the conv->bn(->relu) units of `resnet.py:93-95,133-141`; cfg[10] = also emit a
-    16-bit copy of the output (returned second, non-differentiable) for a following convolution.
+    """conv (+ bias) -> BatchNorm2d -> act -> MaxPool(pool), one layer per call, configured by a `ConvUnit`.
     Input: the fp32 NCHW image batch (first layer; optional fused Normalize) or an fp32 NHWC activation (a 16-bit copy
     attached to it as `._eoe16` by the producing op is used instead of casting); output: fp32 NHWC [n, Ho/p, Wo/p, cout], or
     the reference's NCHW-flattened [n, cout*(Ho/p)*(Wo/p)] (`cnn.py:83`) if flat_out.
@@ -1447,22 +1517,12 @@ class ConvBnActPoolFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, cfg):
         _chk(x, conv_w, conv_b, bn_w, bn_b, rm, rv)
-        training, eps, momentum, pool, is_image, mean, std, flat_out = cfg[:8]
-        kh, kw, stride, pad = cfg[8] if len(cfg) > 8 else (5, 5, 1, 2)
-        slope = float(cfg[9]) if len(cfg) > 9 else 0.01
-        # cfg[11]: also return the input itself (third output).  A residual block hands THAT to its junction as the shortcut,
-        # so the junction's gradient for the shortcut arrives here (backward's d_pass) and the dgrad GEMM accumulates onto
-        # it -- instead of autograd adding the two gradients of the block input with a separate elementwise pass
-        passthrough = bool(cfg[11]) if len(cfg) > 11 else False
+        training, mean, std, passthrough = cfg.training, cfg.mean, cfg.std, bool(cfg.passthrough)
         x_in = x
         x16 = getattr(x, "_eoe16", None)
         x = x.contiguous().float()
-        cout, cin = conv_w.shape[0], conv_w.shape[1]
-        if is_image:
-            n, _, Hi, Wi = x.shape
-        else:
-            n, Hi, Wi, _ = x.shape
-        H, W = (Hi + 2 * pad - kh) // stride + 1, (Wi + 2 * pad - kw) // stride + 1       # conv output grid
+        s = _conv_shape(x, conv_w, cfg)
+        n, H, W, cin, cout, is_image, Hi, Wi, kh, kw, stride, pad = s.n, s.H, s.W, s.cin, s.cout, s.is_image, s.Hi, s.Wi, s.kh, s.kw, s.stride, s.pad
         M, kp, dev, dt = n * H * W, _conv_kp(cin, kh * kw), x.device, _compute_dtype
         code = dtype_code(dt)
         implicit = _implicit_conv and (not is_image) and (cin % 64 == 0 or cin in (8, 16, 32))
@@ -1500,7 +1560,7 @@ class ConvBnActPoolFunction(torch.autograd.Function):
             w16, _, _ = _conv_weight_copies(conv_w)
             if x16 is None or x16.dtype != dt or x16.shape != x.shape:
                 if getattr(x_in, "_eoe_unwritten", False):
-                    raise RuntimeError("this activation only exists as its 16-bit copy (cfg[12] of the producing layer) and that copy does not fit")
+                    raise RuntimeError("this activation only exists as its 16-bit copy (only16 of the producing layer) and that copy does not fit")
                 x16 = cast16(x.view(-1, cin)).view(n, Hi, Wi, cin)
             operand = x16
             conv_gemm_fwd(x16, w16, y, (n, Hi, Wi, cin, kh, kw, stride, pad, H, W), bias=conv_b, colstats_ws=part)
@@ -1510,42 +1570,10 @@ class ConvBnActPoolFunction(torch.autograd.Function):
             check(lib.eoe_im2col(_p(x), 1 if is_image else 2, _p(mean), _p(std), _p(operand), n, cin, Hi, Wi, kh, kw, stride, pad,
                                  kp, code, _stream()), "eoe_im2col")
             gemm_nt(operand, w16, y, bias=conv_b, colstats_ws=part)
-        stats = torch.empty(2 * cout, dtype=torch.float32, device=dev)
-        sums = scratch("bn_sums", (BN_SCRATCH * cout,), torch.float32, dev)
-        if part is not None:
-            check(lib.eoe_bn_stats_partials(_p(part), R, _p(sums), _p(stats), _p(rm), _p(rv), _p(nbt), M, cout, float(eps),
-                                            float(momentum), _stream()), "eoe_bn_stats_partials")
-        else:
-            check(lib.eoe_bn_stats(_p(y), _p(sums), _p(stats), _p(rm), _p(rv), _p(nbt), M, cout, float(eps), float(momentum),
-                                   1 if training else 0, _stream()), "eoe_bn_stats")
-        want16 = bool(cfg[10]) if len(cfg) > 10 else False
-        idx = None
-        if isinstance(pool, tuple):
-            # overlapping MaxPool2d(k, s, p) fused behind BN + act: the pre-pool activation is never written (resnet.py:93-96)
-            pk, pstride, ppad = pool
-            Ho, Wo = (H + 2 * ppad - pk) // pstride + 1, (W + 2 * ppad - pk) // pstride + 1
-            out = torch.empty((n, Ho, Wo, cout), dtype=torch.float32, device=dev)
-            out16 = torch.empty((n, Ho, Wo, cout), dtype=dt, device=dev) if (want16 and _implicit_conv) else None
-            idx = torch.empty((n, Ho, Wo, cout), dtype=torch.uint8, device=dev)
-            check(lib.eoe_bn_act_maxpool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out), _p(out16), _p(idx), n, H, W, cout, pk,
-                                             pstride, ppad, slope, ycode, _stream()), "eoe_bn_act_maxpool_fwd")
-        else:
-            Ho, Wo = H // pool, W // pool
-            out = torch.empty((n, cout * Ho * Wo) if flat_out else (n, Ho, Wo, cout), dtype=torch.float32, device=dev)
-            # a 16-bit copy of the output for the next convolution's implicit GEMM (saves that layer a cast pass)
-            out16 = torch.empty((n, Ho, Wo, cout), dtype=dt, device=dev) if (want16 and _implicit_conv and not flat_out) else None
-            only16 = out16 is not None and len(cfg) > 12 and bool(cfg[12])
-            if only16:
-                # the output feeds ONE consumer that reads the 16-bit copy only (a BasicBlock's conv1 -> bn1 -> relu -> conv2): the fp32
-                # tensor is allocated for autograd's bookkeeping but never written (4 of the pass's 10 bytes per element)
-                check(lib.eoe_bn_act_pool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out16), None, n, H, W, cout, pool,
-                                              0, 0, slope, ycode, _stream()), "eoe_bn_act_pool_fwd")
-            else:
-                check(lib.eoe_bn_act_pool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out), _p(out16), n, H, W, cout, pool,
-                                              1 if flat_out else 0, 1, slope, ycode, _stream()), "eoe_bn_act_pool_fwd")
+        out, out16, idx, stats = _bn_act_pool_fwd(y, part, R, bn_w, bn_b, rm, rv, nbt, cfg.eps, cfg.momentum, s, ycode,
+                                                  dt16=dt if (cfg.want16 and _implicit_conv) else None, only16=cfg.only16)
         ctx.save_for_backward(operand, y, stats, conv_w, conv_b, bn_w, bn_b, idx)
-        ctx.cfg = (n, H, W, cin, cout, kp, pool, flat_out, training, is_image, Hi, Wi, kh, kw, stride, pad, slope, implicit)
-        ctx.has16, ctx.passthrough = out16 is not None, passthrough
+        ctx.shape, ctx.kp, ctx.implicit, ctx.passthrough = s, kp, implicit, passthrough
         if out16 is None and not passthrough:
             return out
         ctx.set_materialize_grads(False)       # else autograd zero-fills a gradient for the 16-bit copy every step
@@ -1558,29 +1586,16 @@ class ConvBnActPoolFunction(torch.autograd.Function):
         return tuple(outs)
 
     @staticmethod
-    def backward(ctx, dout, *more):
-        d_pass = more[-1] if (ctx.passthrough and more) else None
-        if dout is None:                         # only the pass-through output was used downstream
-            return (d_pass,) + (None,) * 8
+    @_with_passthrough
+    def backward(ctx, dout, d_pass):
         operand, y, stats, conv_w, conv_b, bn_w, bn_b, idx = ctx.saved_tensors
-        n, H, W, cin, cout, kp, pool, flat_out, training, is_image, Hi, Wi, kh, kw, stride, pad, slope, implicit = ctx.cfg
+        s, kp, implicit = ctx.shape, ctx.kp, ctx.implicit
+        n, H, W, cin, cout, is_image, Hi, Wi, kh, kw, stride, pad = s.n, s.H, s.W, s.cin, s.cout, s.is_image, s.Hi, s.Wi, s.kh, s.kw, s.stride, s.pad
         dev, dt = y.device, operand.dtype
         code = dtype_code(dt)
-        ycode = code | (_lib.EOE_Y16 if y.dtype != torch.float32 else 0)
         M = n * H * W
-        dout = dout.contiguous().float()
-        dy16 = torch.empty((M, cout), dtype=dt, device=dev)
-        dg = _grad_target(bn_w) if bn_w is not None else None
-        db = _grad_target(bn_b) if bn_b is not None else None
-        red = scratch("bn_red", (BN_SCRATCH * cout,), torch.float32, dev)
-        if isinstance(pool, tuple):
-            check(lib.eoe_bn_act_maxpool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(idx), _p(red), _p(dy16), _p(dg), _p(db),
-                                             n, H, W, cout, pool[0], pool[1], pool[2], 1 if training else 0, slope, ycode, _stream()),
-                  "eoe_bn_act_maxpool_bwd")
-        else:
-            check(lib.eoe_bn_act_pool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(red), _p(dy16), 0, _p(dg), _p(db), n, H,
-                                          W, cout, pool, 1 if flat_out else 0, 1 if training else 0, 0, slope, ycode, _stream()),
-                  "eoe_bn_act_pool_bwd")
+        dy16, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, dt, 0,
+                                        code | (_lib.EOE_Y16 if y.dtype != torch.float32 else 0))
         dw = _grad_target(conv_w)
         _side_ctx = _conv_wgrad_side_begin(dy16, operand) if CONV_ASYNC_WGRAD else None
         if implicit == 2:
@@ -1611,8 +1626,7 @@ class ConvBnActPoolFunction(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0] and not is_image:
             _, w16t, w16d = _conv_weight_copies(conv_w)
-            acc = (d_pass is not None and d_pass.dtype == torch.float32 and d_pass.is_contiguous()
-                   and d_pass.shape == (n, Hi, Wi, cin))
+            acc = _accumulates(d_pass, s)
             if _implicit_conv and stride == 1 and kh == kw and cout % 64 == 0:
                 # dx = conv of dy with the flipped kernel: the same implicit GEMM, gathering from dy16 [n, H, W, cout];
                 # with a shortcut gradient it accumulates onto that tensor (C += in the epilogue)
@@ -1629,9 +1643,7 @@ class ConvBnActPoolFunction(torch.autograd.Function):
                       "eoe_col2im")
                 if acc:
                     d_pass = None
-        if d_pass is not None:
-            dx = d_pass if dx is None else dx.add_(d_pass)
-        return dx, dw, dcb, dg, db, None, None, None, None
+        return dx, dw, dcb, dg, db, d_pass
 
 
 # A convolution's weight-gradient GEMM (+ its unpack / reduce kernels) on a side stream: nothing in the backward sweep reads the weight
@@ -1674,17 +1686,16 @@ def _conv_wgrad_join():
 
 def conv_bn_act_pool(x, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, cfg):
     """ConvBnActPoolFunction + the 16-bit copy of its output attached as `._eoe16` (consumed by the next convolution)"""
+    cfg = cfg if isinstance(cfg, ConvUnit) else ConvUnit(*cfg)          # (a plain tuple of the leading fields)
     if _parity:
         return ConvBnActPoolParityFunction.apply(x, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, cfg)
     r = ConvBnActPoolFunction.apply(x, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, cfg)
-    passthrough = bool(cfg[11]) if len(cfg) > 11 else False
+    passthrough = bool(cfg.passthrough)
     if not isinstance(r, tuple):
         return r
     out = r[0]
     if len(r) - (1 if passthrough else 0) == 2:
-        out._eoe16 = r[1]
-        if len(cfg) > 12 and cfg[12] and not (isinstance(cfg[3], tuple) or cfg[7]):
-            out._eoe_unwritten = True          # (ConvBnActPoolFunction.forward, only16: the values live in the 16-bit copy alone)
+        out._eoe16 = r[1]          # (where only16 held, forward has marked `out` as `._eoe_unwritten`)
     if passthrough:
         x16 = getattr(x, "_eoe16", None)
         if x16 is not None:
@@ -1702,31 +1713,17 @@ class BnActFunction(torch.autograd.Function):
         training, eps, momentum = cfg
         y = y.contiguous().float()
         n, C = y.shape
-        dev = y.device
-        stats = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        sums = scratch("bn_sums", (BN_SCRATCH * C,), torch.float32, dev)
-        check(lib.eoe_bn_stats(_p(y), _p(sums), _p(stats), _p(rm), _p(rv), _p(nbt), n, C, float(eps), float(momentum),
-                               1 if training else 0, _stream()), "eoe_bn_stats")
-        out = torch.empty_like(y)
-        check(lib.eoe_bn_act_pool_fwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(out), None, n, 1, 1, C, 1, 0, 1, 0.01,
-                                      dtype_code(_compute_dtype), _stream()), "eoe_bn_act_pool_fwd")
+        # the [n, C] matrix as n maps of 1x1 with pool 1; the slope is nn.LeakyReLU's default, which cnn.py:85 leaves as it is
+        s = _ConvShape(n, 1, 1, C, 1, False, training, 0.01)
+        out, _, _, stats = _bn_act_pool_fwd(y, None, 0, bn_w, bn_b, rm, rv, nbt, eps, momentum, s, dtype_code(_compute_dtype))
         ctx.save_for_backward(y, stats, bn_w, bn_b)
-        ctx.training = training
-        return out
+        ctx.shape = s
+        return out.view(n, C)
 
     @staticmethod
     def backward(ctx, dout):
         y, stats, bn_w, bn_b = ctx.saved_tensors
-        n, C = y.shape
-        dev = y.device
-        dout = dout.contiguous().float()
-        dy = torch.empty_like(y)
-        dg = _grad_target(bn_w) if bn_w is not None else None
-        db = _grad_target(bn_b) if bn_b is not None else None
-        red = scratch("bn_red", (BN_SCRATCH * C,), torch.float32, dev)
-        check(lib.eoe_bn_act_pool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(red), _p(dy), 1, _p(dg), _p(db), n, 1, 1,
-                                      C, 1, 0, 1 if ctx.training else 0, 0, 0.01, dtype_code(_compute_dtype), _stream()),
-              "eoe_bn_act_pool_bwd")
+        dy, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, None, ctx.shape, torch.float32, 1, dtype_code(_compute_dtype))
         return dy, dg, db, None, None, None, None
 
 

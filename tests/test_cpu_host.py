@@ -293,3 +293,30 @@ def test_late_gradient_writes_only_into_tensors_autograd_adopts():
     finally:
         ops.async_wgrad_blockers = old
     assert ops._late_write_ok(leaves(), [True] * 3)
+
+
+def test_conv_unit_reads_the_legacy_tuples():
+    """ops.ConvUnit(*t) of the positional tuples the callers and the GPU tests have passed (8, 10, 11 and 13 entries) gives what the
+    slot arithmetic gave: slots 8-12 default to (5, 5, 1, 2), 0.01, False, False, False"""
+    from eoe_amd import ops
+    mean, std = torch.tensor([0.5, 0.4, 0.3]), torch.tensor([0.2, 0.2, 0.2])
+    assert issubclass(ops.ConvUnit, tuple)
+    assert ops.ConvUnit._fields == ("training", "eps", "momentum", "pool", "is_image", "mean", "std", "flat_out",
+                                    "kernel", "slope", "want16", "passthrough", "only16")
+    u = ops.ConvUnit(*(True, 1e-4, 0.1, 2, True, mean, std, True))                                     # tests/test_gpu_cnn.py
+    assert (u.training, u.eps, u.momentum, u.pool, u.is_image, u.flat_out) == (True, 1e-4, 0.1, 2, True, True)
+    assert u.mean is mean and u.std is std
+    assert (u.kernel, u.slope, u.want16, u.passthrough, u.only16) == ((5, 5, 1, 2), 0.01, False, False, False)
+    u = ops.ConvUnit(*(True, 1e-5, 0.1, 1, False, None, None, False, (3, 3, 2, 1), 0.0))               # tests/test_gpu_resnet.py
+    assert (u.training, u.eps, u.momentum, u.pool, u.is_image, u.mean, u.std, u.flat_out) == (True, 1e-5, 0.1, 1, False, None, None, False)
+    assert (u.kernel, u.slope, u.want16, u.passthrough, u.only16) == ((3, 3, 2, 1), 0.0, False, False, False)
+    u = ops.ConvUnit(*(True, 1e-5, 0.1, (3, 2, 1), True, mean, std, False, (7, 7, 2, 3), 0.0, True))   # the max-pool stem; CNN32's layers
+    assert (u.pool, u.is_image, u.flat_out) == ((3, 2, 1), True, False)
+    assert (u.kernel, u.slope, u.want16, u.passthrough, u.only16) == ((7, 7, 2, 3), 0.0, True, False, False)
+    u = ops.ConvUnit(*(False, 1e-5, 0.1, 1, False, None, None, False, (3, 3, 1, 1), 1.0, True, True, True))    # models/resnet.py
+    assert (u.training, u.pool, u.is_image, u.flat_out) == (False, 1, False, False)
+    assert (u.kernel, u.slope, u.want16, u.passthrough, u.only16) == ((3, 3, 1, 1), 1.0, True, True, True)
+    u = ops.ConvUnit(*(True, 1e-4, 0.1, 2, False, None, None, False, (3, 3, 1, 1)))                    # 9 entries: the kernel alone
+    assert u.kernel == (3, 3, 1, 1) and u.slope == 0.01 and not (u.want16 or u.passthrough or u.only16)
+    with pytest.raises(TypeError):
+        ops.ConvUnit(True, 1e-4, 0.1, 2, False, None, None)                                            # the first eight have no default
