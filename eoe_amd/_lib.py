@@ -242,6 +242,10 @@ SIGNATURES = {
     "eoe_grayscale_u8": [_vp, _vp, _i64, _vp],
     "eoe_augment_resize_batch": [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                  C.c_int, C.c_int, _f32, C.c_uint64, _vp],
+    "eoe_ragged_augment_batch": [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_uint64, _vp],
+    "eoe_ragged_crop_flip_u8": [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_ragged_color_jitter_crop_u8": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_ragged_resize_pass_u8": [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, _vp],
     "eoe_set_moments_u8": [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp],
     "eoe_gcn_normalize": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "eoe_pool_sqdist_workspace": [_i64, C.c_int, C.c_int, C.POINTER(_sz)],

@@ -228,6 +228,205 @@ extern "C" int eoe_crop_flip_u8(const uint8_t* src, int64_t n_src, int Hs, int W
     return eoe_crop_flip_u8_c(src, n_src, Hs, Ws, 3, params, out, n, Ho, Wo, flip_first, stream);
 }
 
+// ---- ragged sets (main/train_imagenet.py:30-34, train_cub.py, train_dtd.py, train_mvtec.py, train_custom.py: Resize(256) keeps the
+// aspect ratio, so every image has its own shape): the images lie back to back in one uint8 arena, image i at arena + offsets[i]
+// (int64), row-major HWC with (H, W) = sizes[2 i], sizes[2 i + 1].  The kernels above compute a slot's image from index * H * W * C;
+// these look (offset, H, W) up.  A workgroup works on ONE slot (blockIdx.x / bps), so params and both table entries are
+// workgroup-uniform: the compiler reads them with scalar loads once, in front of the pixel loop, not per pixel.  bps workgroups
+// share a slot's outputs with a stride loop, which keeps the launch as wide as the uniform kernels' (8192 workgroups) at 256
+// slots.  No row is assumed aligned (W * C is odd for most images): the loads are byte loads, or the 4-byte memcpy of gather4_c1.
+// Statements of the fp32 tail are those of augment_kernel / augment_c1_kernel, in front of the `fp contract(off)` pragma below
+// like them: the results are equal bit for bit (tests/test_gpu_ragged.py).
+namespace {
+
+struct RaggedImage { const uint8_t* base; int H, W; };                  // base NULL: the index lies outside the set -> all padding
+
+__device__ __forceinline__ RaggedImage ragged_image(const uint8_t* __restrict__ arena, const long long* __restrict__ offsets,
+                                                    const int32_t* __restrict__ sizes, long long n_src, int idx) {
+    RaggedImage im = {nullptr, 0, 0};
+    if (idx >= 0 && (long long)idx < n_src) {
+        im.base = arena + offsets[idx];
+        im.H = sizes[2 * idx];
+        im.W = sizes[2 * idx + 1];
+    }
+    return im;
+}
+
+// source column of output column x of a slot: s0 + dir * x (crop_flip_src's two flip orders)
+__device__ __forceinline__ void ragged_columns(int left, int flip, int flip_first, int Ws, int Wo, int& s0, int& dir) {
+    if (!flip) { s0 = left; dir = 1; }
+    else if (flip_first) { s0 = Ws - 1 - left; dir = -1; }               // flip the source, then crop
+    else { s0 = left + Wo - 1; dir = -1; }                               // crop, then flip the crop
+}
+
+// ToTensor, noise and Normalize of byte v, element e of slot b, channel c: augment_kernel's statements
+__device__ __forceinline__ float ragged_to_float(int v, unsigned long long e, int b, int c, const float* __restrict__ mean,
+                                                 const float* __restrict__ stdv, float noise_std, unsigned long long seed) {
+    float a = (float)v / 255.0f;                                             // ToTensor
+    if (noise_std > 0.f) {
+        const unsigned long long z = splitmix64((seed << 40) + ((unsigned long long)b << 18) + e);
+        const float u1 = (float)((z >> 40) + 1ull) * (1.0f / 16777216.0f);          // (0, 1]
+        const float u2 = (float)((z >> 16) & 0xFFFFFFull) * (1.0f / 16777216.0f);   // [0, 1)
+        a += noise_std * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+    }
+    if (mean) a = (a - mean[c]) / stdv[c];
+    return a;
+}
+
+// gather4_c1 on a row that is already looked up (NULL: padding): v[k] = the byte under output column x0 + k
+__device__ __forceinline__ void ragged_gather4(const uint8_t* __restrict__ row, int Ws, int s0, int dir, int x0, int Wo, int v[4]) {
+    v[0] = v[1] = v[2] = v[3] = 0;
+    if (!row) return;
+    const int sa = s0 + dir * x0, sb = s0 + dir * (x0 + 3);
+    const int lo = dir > 0 ? sa : sb;
+    if (x0 + 3 < Wo && lo >= 0 && lo + 3 < Ws) {
+        unsigned w;
+        __builtin_memcpy(&w, row + lo, 4);                               // any alignment
+        if (dir < 0) w = __builtin_bswap32(w);
+        v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int sx = sa + dir * k;
+        if (x0 + k < Wo && sx >= 0 && sx < Ws) v[k] = row[sx];
+    }
+}
+
+// three channels, a thread per output pixel of its slot; F32: fp32 NCHW with the tail, else uint8 NHWC
+template <bool F32>
+__global__ __launch_bounds__(256) void ragged_c3_kernel(const uint8_t* __restrict__ arena, const long long* __restrict__ offsets,
+                                                        const int32_t* __restrict__ sizes, long long n_src, const int32_t* __restrict__ params,
+                                                        const float* __restrict__ mean, const float* __restrict__ stdv, void* __restrict__ out_,
+                                                        int bps, int Ho, int Wo, int flip_first, float noise_std, unsigned long long seed) {
+    const int b = blockIdx.x / bps, part = blockIdx.x % bps;
+    const int idx = params[b * 4 + 0], top = params[b * 4 + 1], left = params[b * 4 + 2], flip = params[b * 4 + 3];
+    const RaggedImage im = ragged_image(arena, offsets, sizes, n_src, idx);
+    int s0, dir;
+    ragged_columns(left, flip, flip_first, im.W, Wo, s0, dir);
+    const int total = Ho * Wo;
+    for (int i = part * 256 + (int)threadIdx.x; i < total; i += bps * 256) {
+        const int x = i % Wo, y = i / Wo;
+        const int sy = top + y, sx = s0 + dir * x;
+        int v[3] = {0, 0, 0};                                                // RandomCrop pads with 0
+        if (im.base && sy >= 0 && sy < im.H && sx >= 0 && sx < im.W) {
+            const uint8_t* p = im.base + ((size_t)sy * im.W + sx) * 3;
+            v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+        }
+        if (F32) {
+            float* out = static_cast<float*>(out_);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned long long e = ((unsigned long long)c * Ho + y) * Wo + x;
+                out[(((size_t)b * 3 + c) * Ho + y) * Wo + x] = ragged_to_float(v[c], e, b, c, mean, stdv, noise_std, seed);
+            }
+        } else {
+            uint8_t* o = static_cast<uint8_t*>(out_) + ((size_t)b * total + i) * 3;
+            o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2];
+        }
+    }
+}
+
+// one channel, a thread per quad of 4 output columns of its slot (augment_c1_kernel / crop_flip_c1_kernel); VEC: the quad leaves as
+// one float4 (F32) or one 4-byte word
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(256) void ragged_c1_kernel(const uint8_t* __restrict__ arena, const long long* __restrict__ offsets,
+                                                        const int32_t* __restrict__ sizes, long long n_src, const int32_t* __restrict__ params,
+                                                        const float* __restrict__ mean, const float* __restrict__ stdv, void* __restrict__ out_,
+                                                        int bps, int Ho, int Wo, int flip_first, float noise_std, unsigned long long seed) {
+    const int b = blockIdx.x / bps, part = blockIdx.x % bps;
+    const int idx = params[b * 4 + 0], top = params[b * 4 + 1], left = params[b * 4 + 2], flip = params[b * 4 + 3];
+    const RaggedImage im = ragged_image(arena, offsets, sizes, n_src, idx);
+    int s0, dir;
+    ragged_columns(left, flip, flip_first, im.W, Wo, s0, dir);
+    const int Q = (Wo + 3) / 4, total = Ho * Q;
+    for (int i = part * 256 + (int)threadIdx.x; i < total; i += bps * 256) {
+        const int x0 = (i % Q) * 4, y = i / Q;
+        const int sy = top + y;
+        const uint8_t* row = (im.base && sy >= 0 && sy < im.H) ? im.base + (size_t)sy * im.W : nullptr;
+        int v[4];
+        ragged_gather4(row, im.W, s0, dir, x0, Wo, v);
+        const size_t at = ((size_t)b * Ho + y) * Wo + x0;
+        if (F32) {
+            float a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = ragged_to_float(v[k], (unsigned long long)y * Wo + (x0 + k), b, 0, mean, stdv, noise_std, seed);
+            float* o = static_cast<float*>(out_) + at;
+            if (VEC) *reinterpret_cast<float4*>(o) = make_float4(a[0], a[1], a[2], a[3]);
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x0 + k < Wo) o[k] = a[k];
+            }
+        } else {
+            uint8_t* o = static_cast<uint8_t*>(out_) + at;
+            if (VEC) *reinterpret_cast<unsigned*>(o) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x0 + k < Wo) o[k] = (uint8_t)v[k];
+            }
+        }
+    }
+}
+
+// workgroups per slot: enough that every thread has an element, at most about 8192 workgroups in all (the uniform kernels' cap)
+int ragged_bps(int n, size_t per_slot) {
+    size_t bps = (per_slot + 255) / 256, cap = 8192 / (size_t)n;
+    if (bps > cap) bps = cap;
+    return bps < 1 ? 1 : (int)bps;
+}
+
+template <bool F32>
+void ragged_crop_launch(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C, const int32_t* params,
+                        const float* mean, const float* stdv, void* out, int n, int Ho, int Wo, int flip_first, float noise_std,
+                        uint64_t seed, void* stream) {
+    const long long* off = reinterpret_cast<const long long*>(offsets);
+    if (C == 3) {
+        const int bps = ragged_bps(n, (size_t)Ho * Wo);
+        hipLaunchKernelGGL(ragged_c3_kernel<F32>, dim3((unsigned)((size_t)n * bps)), dim3(256), 0, (hipStream_t)stream, arena, off, sizes,
+                           (long long)n_src, params, mean, stdv, out, bps, Ho, Wo, flip_first, noise_std, (unsigned long long)seed);
+    } else {
+        const int bps = ragged_bps(n, (size_t)Ho * ((Wo + 3) / 4));
+        const bool vec = Wo % 4 == 0 && (uintptr_t)out % (F32 ? 16 : 4) == 0;
+        hipLaunchKernelGGL((vec ? ragged_c1_kernel<F32, true> : ragged_c1_kernel<F32, false>), dim3((unsigned)((size_t)n * bps)), dim3(256), 0,
+                           (hipStream_t)stream, arena, off, sizes, (long long)n_src, params, mean, stdv, out, bps, Ho, Wo, flip_first,
+                           noise_std, (unsigned long long)seed);
+    }
+}
+
+}  // namespace
+
+extern "C" int eoe_ragged_augment_batch(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C,
+                                        const int32_t* params, const float* mean, const float* stdv, float* out, int n, int Ho, int Wo,
+                                        int flip_first, float noise_std, uint64_t seed, void* stream) {
+    EOE_CHECK_ARG(C == 1 || C == 3, "ragged_augment_batch: C must be 1 or 3, not %d", C);
+    EOE_CHECK_ARG(n >= 0 && n_src > 0 && Ho > 0 && Wo > 0, "ragged_augment_batch: bad args");
+    if (n == 0) return 0;
+    EOE_CHECK_ARG(arena && offsets && sizes && params && out, "ragged_augment_batch: bad args");
+    EOE_CHECK_ARG((mean == nullptr) == (stdv == nullptr), "ragged_augment_batch: mean/std must both be given or both NULL");
+    EOE_CHECK_ARG(n < (1 << 22) && (size_t)3 * Ho * Wo < (1u << 18) && seed < (1ull << 24) && noise_std >= 0.f,
+                  "ragged_augment_batch: n < 2^22, 3*Ho*Wo < 2^18, seed < 2^24 (the counter layout of the noise generator)");
+    ProfScope ps("ragged_augment", 0, (double)C * n * Ho * Wo + 4.0 * C * n * Ho * Wo, stream);
+    ragged_crop_launch<true>(arena, offsets, sizes, n_src, C, params, mean, stdv, out, n, Ho, Wo, flip_first, noise_std, seed, stream);
+    EOE_CHECK_LAUNCH("ragged_augment_batch");
+    return 0;
+}
+
+extern "C" int eoe_ragged_crop_flip_u8(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C,
+                                       const int32_t* params, uint8_t* out, int n, int Ho, int Wo, int flip_first, void* stream) {
+    EOE_CHECK_ARG(C == 1 || C == 3, "ragged_crop_flip_u8: C must be 1 or 3, not %d", C);
+    EOE_CHECK_ARG(n >= 0 && n_src > 0 && Ho > 0 && Wo > 0, "ragged_crop_flip_u8: bad args");
+    if (n == 0) return 0;
+    EOE_CHECK_ARG(arena && offsets && sizes && params && out, "ragged_crop_flip_u8: bad args");
+    EOE_CHECK_ARG((const void*)arena != (const void*)out, "ragged_crop_flip_u8: out must not alias the arena");
+    EOE_CHECK_ARG(n < (1 << 22) && (size_t)Ho * Wo < (1u << 28), "ragged_crop_flip_u8: n < 2^22 and Ho*Wo < 2^28");
+    ProfScope ps("ragged_crop_flip", 0, 2.0 * C * n * Ho * Wo, stream);
+    ragged_crop_launch<false>(arena, offsets, sizes, n_src, C, params, nullptr, nullptr, out, n, Ho, Wo, flip_first, 0.f, 0, stream);
+    EOE_CHECK_LAUNCH("ragged_crop_flip_u8");
+    return 0;
+}
+
 // ---- CLIP's per-sample upsample inside the chain (main/train_clip_cifar.py:26-35, train_clip_fmnist.py:27-36, train_clip_mnist.py:25-29):
 //   ... RandomCrop(S, padding) -> RandomHorizontalFlip -> Resize(P, BICUBIC) -> CenterCrop(P) -> convert("RGB") -> ToTensor -> noise -> Normalize
 // The resize comes after the random crop / flip, so it runs per sample per step.  A slot's source is only S x S x C bytes (3 KB at
@@ -503,6 +702,41 @@ __global__ __launch_bounds__(256) void resize_pass_kernel(const uint8_t* __restr
     }
 }
 
+// resize_pass_kernel over a ragged set, all images in ONE launch: image i is src + offs[2 i] viewed as [outer, axis_in, inner] ->
+// dst + offs[2 i + 1] as [outer, axis_out, inner], with desc[8 i ..] = (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, 0);
+// bounds_at / kk_at are positions in `taps`, the int32 arena that holds the host's eoe_resize_coeffs tables, one per distinct
+// (in, out, filter) of the set.  bpi workgroups share an image's output bytes.  axis_in == axis_out: Pillow skips the pass, the
+// image is copied.  Integer arithmetic only; nothing about the taps is computed here.
+__global__ __launch_bounds__(256) void resize_pass_ragged_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                 const long long* __restrict__ offs, const int32_t* __restrict__ desc,
+                                                                 const int32_t* __restrict__ taps, int bpi) {
+    const int img = blockIdx.x / bpi, part = blockIdx.x % bpi;
+    const int32_t* d = desc + (size_t)img * 8;
+    const int outer = d[0], axis_in = d[1], axis_out = d[2], inner = d[3], ksize = d[6];
+    const uint8_t* s = src + offs[2 * (size_t)img];
+    uint8_t* o = dst + offs[2 * (size_t)img + 1];
+    const size_t total = (size_t)outer * axis_out * inner;
+    const size_t first = (size_t)part * 256 + threadIdx.x, step = (size_t)bpi * 256;
+    if (axis_in == axis_out) {
+        for (size_t i = first; i < total; i += step) o[i] = s[i];
+        return;
+    }
+    const int32_t* bounds = taps + d[4];
+    const int32_t* kk = taps + d[5];
+    for (size_t i = first; i < total; i += step) {
+        const int in = (int)(i % inner);
+        const int xx = (int)((i / inner) % axis_out);
+        const size_t r = i / ((size_t)inner * axis_out);
+        const int xmin = bounds[2 * xx], cnt = bounds[2 * xx + 1];
+        const uint8_t* p = s + (r * axis_in + xmin) * inner + in;
+        const int32_t* k = kk + (size_t)xx * ksize;
+        int ss = 1 << (RESIZE_PRECISION_BITS - 1);
+        for (int x = 0; x < cnt; ++x) ss += (int)p[(size_t)x * inner] * k[x];
+        ss >>= RESIZE_PRECISION_BITS;
+        o[i] = (uint8_t)(ss < 0 ? 0 : (ss > 255 ? 255 : ss));
+    }
+}
+
 // Pillow's C code is compiled without fused multiply-adds; hipcc contracts a * b + c by default -- also through __fmul_rn /
 // __fadd_rn, which are plain operators in HIP's headers -- and a blend that lands within one ulp of an integer then truncates
 // to the neighbouring byte (saturation 0.99 on a gray level of 100: 100 - 99.00000095 = 0.99999905 -> 0 instead of 1)
@@ -620,7 +854,97 @@ __global__ __launch_bounds__(256) void jitter_kernel(const uint8_t* __restrict__
     }
 }
 
+// ColorJitter of a whole ragged image followed by crop / flip, without writing the jittered image: every op is pointwise once the
+// contrast op's gray mean is known.  MODE 0 is jitter_kernel<0> over the slot's whole image (its own H x W); MODE 1 applies
+// jitter_pixel only under the crop window, the padding stays 0 (RandomCrop pads after the jitter).
+template <int MODE>
+__global__ __launch_bounds__(256) void jitter_ragged_kernel(const uint8_t* __restrict__ arena, const long long* __restrict__ offsets,
+                                                            const int32_t* __restrict__ sizes, long long n_src, const int32_t* __restrict__ params,
+                                                            const float* __restrict__ factors, const int32_t* __restrict__ order,
+                                                            int32_t* __restrict__ gray_mean, uint8_t* __restrict__ out, int bps, int Ho, int Wo,
+                                                            int flip_first) {
+    const int slot = MODE == 0 ? (int)blockIdx.x : (int)blockIdx.x / bps;
+    const float f[4] = {factors[slot * 4], factors[slot * 4 + 1], factors[slot * 4 + 2], factors[slot * 4 + 3]};
+    const int ord[4] = {order[slot * 4], order[slot * 4 + 1], order[slot * 4 + 2], order[slot * 4 + 3]};
+    const RaggedImage im = ragged_image(arena, offsets, sizes, n_src, params[slot * 4]);
+    if (MODE == 0) {
+        __shared__ unsigned long long part[256];
+        const size_t HW = im.base ? (size_t)im.H * im.W : 0;
+        unsigned long long acc = 0;
+        for (size_t i = threadIdx.x; i < HW; i += blockDim.x) {
+            int r = im.base[i * 3], g = im.base[i * 3 + 1], b = im.base[i * 3 + 2];
+            jitter_pixel(r, g, b, f, ord, 0, 1);                 // everything in front of the contrast op
+            acc += (unsigned long long)gray_l(r, g, b);
+        }
+        part[threadIdx.x] = acc;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+            __syncthreads();
+        }
+        // ImageEnhance.Contrast: int(mean + 0.5) of the L image
+        if (threadIdx.x == 0) gray_mean[slot] = HW ? (int)((2 * part[0] + (unsigned long long)HW) / (2ull * HW)) : 0;
+    } else {
+        const int partn = blockIdx.x % bps;
+        const int top = params[slot * 4 + 1], left = params[slot * 4 + 2], flip = params[slot * 4 + 3];
+        const int gm = gray_mean[slot];
+        int s0, dir;
+        ragged_columns(left, flip, flip_first, im.W, Wo, s0, dir);
+        const int total = Ho * Wo;
+        for (int i = partn * 256 + (int)threadIdx.x; i < total; i += bps * 256) {
+            const int x = i % Wo, y = i / Wo;
+            const int sy = top + y, sx = s0 + dir * x;
+            int r = 0, g = 0, b = 0;
+            if (im.base && sy >= 0 && sy < im.H && sx >= 0 && sx < im.W) {
+                const uint8_t* p = im.base + ((size_t)sy * im.W + sx) * 3;
+                r = p[0]; g = p[1]; b = p[2];
+                jitter_pixel(r, g, b, f, ord, gm, 4);
+            }
+            uint8_t* o = out + ((size_t)slot * total + i) * 3;
+            o[0] = (uint8_t)r; o[1] = (uint8_t)g; o[2] = (uint8_t)b;
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int eoe_ragged_color_jitter_crop_u8(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src,
+                                               const int32_t* params, const float* factors, const int32_t* order,
+                                               int32_t* gray_mean_scratch, uint8_t* out, int n, int Ho, int Wo, int flip_first, void* stream) {
+    EOE_CHECK_ARG(n >= 0 && n_src > 0 && Ho > 0 && Wo > 0, "ragged_color_jitter_crop: bad args");
+    if (n == 0) return 0;
+    EOE_CHECK_ARG(arena && offsets && sizes && params && factors && order && gray_mean_scratch && out, "ragged_color_jitter_crop: bad args");
+    EOE_CHECK_ARG((const void*)arena != (const void*)out, "ragged_color_jitter_crop: out must not alias the arena");
+    EOE_CHECK_ARG(n < (1 << 22) && (size_t)Ho * Wo < (1u << 28), "ragged_color_jitter_crop: n < 2^22 and Ho*Wo < 2^28");
+    const long long* off = reinterpret_cast<const long long*>(offsets);
+    ProfScope ps("ragged_jitter_crop", 0, 3.0 * 2.0 * n * Ho * Wo, stream);
+    hipLaunchKernelGGL(jitter_ragged_kernel<0>, dim3(n), dim3(256), 0, (hipStream_t)stream, arena, off, sizes, (long long)n_src, params, factors,
+                       order, gray_mean_scratch, out, 1, Ho, Wo, flip_first);
+    EOE_CHECK_LAUNCH("ragged_color_jitter_mean");
+    const int bps = ragged_bps(n, (size_t)Ho * Wo);
+    hipLaunchKernelGGL(jitter_ragged_kernel<1>, dim3((unsigned)((size_t)n * bps)), dim3(256), 0, (hipStream_t)stream, arena, off, sizes,
+                       (long long)n_src, params, factors, order, gray_mean_scratch, out, bps, Ho, Wo, flip_first);
+    EOE_CHECK_LAUNCH("ragged_color_jitter_crop");
+    return 0;
+}
+
+extern "C" int eoe_ragged_resize_pass_u8(const uint8_t* src, uint8_t* dst, const int64_t* offs, const int32_t* desc, const int32_t* taps,
+                                         int n, int64_t max_out_bytes, void* stream) {
+    EOE_CHECK_ARG(n >= 0 && max_out_bytes >= 0, "ragged_resize_pass: bad args");
+    if (n == 0 || max_out_bytes == 0) return 0;
+    EOE_CHECK_ARG(src && dst && offs && desc && taps, "ragged_resize_pass: bad args");
+    EOE_CHECK_ARG((const void*)src != (const void*)dst, "ragged_resize_pass: dst must not alias src");
+    // workgroups per image: four output bytes per thread of the largest image, at most 64, and at most about 2^20 workgroups
+    int64_t bpi = (max_out_bytes + 1023) / 1024;
+    if (bpi > 64) bpi = 64;
+    if (bpi * n > (1 << 20)) bpi = (1 << 20) / n;
+    if (bpi < 1) bpi = 1;
+    ProfScope ps("ragged_resize_pass", 0, 0.0, stream);
+    hipLaunchKernelGGL(resize_pass_ragged_kernel, dim3((unsigned)((size_t)n * bpi)), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       reinterpret_cast<const long long*>(offs), desc, taps, (int)bpi);
+    EOE_CHECK_LAUNCH("ragged_resize_pass");
+    return 0;
+}
 
 extern "C" int eoe_resize_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk, int ksize_cap, int* ksize_out) {
     EOE_CHECK_ARG(in_size > 0 && out_size > 0 && (filter == EOE_RESIZE_BILINEAR || filter == EOE_RESIZE_BICUBIC),

@@ -111,15 +111,169 @@ def _channels(src_u8, who):
     return C
 
 
+def resized_hw(H, W, size):
+    """the (h, w) that `torchvision.transforms.Resize(size)` gives an H x W image (`transforms/functional.py`
+    `_compute_resized_output_size`): an int scales the SHORTER side to `size` and the other one to int(size * long / short) -- the
+    image is unchanged when the shorter side equals `size` already --, a pair is (h, w) itself"""
+    H, W = int(H), int(W)
+    if not isinstance(size, int):
+        h, w = size
+        return int(h), int(w)
+    short, long = (W, H) if W <= H else (H, W)
+    if short == size:
+        return H, W
+    new_long = int(size * long / short)
+    return (new_long, size) if W <= H else (size, new_long)
+
+
+class RaggedImageSet:
+    """uint8 HWC images of DIFFERENT sizes and one channel count (1 or 3), as the 224 x 224 tasks have them after `Resize(256)`
+    (`main/train_imagenet.py:30-34`: 256 x W' or H' x 256 per image).  Layout:
+      `arena`        one flat uint8 tensor, the images back to back, each row-major HWC.  Every image STARTS at a multiple of
+                     16 bytes (`ALIGN`; the gap is zeros) and the arena's length is a multiple of 16, so an equal-size set is a
+                     strided view.  Rows are not aligned -- W * C is odd for most images -- and no kernel assumes they are.
+      `offsets`      int64 [n] on the arena's device: the byte at which image i starts (int64: one ImageNet class after
+                     Resize(256) is about 340 MB, an OE pool more)
+      `sizes_dev`    int32 [n, 2] = (H_i, W_i) on the arena's device
+      `sizes`, `offsets_host`   host copies (numpy): crop origins are drawn and launches sized on the host
+    Usable without a GPU (packing, indexing, `.to`); the kernels that read it (`resize_u8`, `augment_batch`, `crop_flip_u8`,
+    `color_jitter_crop_u8`) need it on one."""
+
+    ALIGN = 16
+
+    def __init__(self, images, device=None):
+        """images: a sequence of uint8 numpy arrays or tensors [H, W], [H, W, 1] or [H, W, 3] (mixed channel counts are refused)"""
+        import numpy as np
+        ts = []
+        for i, im in enumerate(images):
+            t = torch.as_tensor(im)
+            if t.dtype != torch.uint8 or t.dim() not in (2, 3):
+                raise ValueError(f"RaggedImageSet: image {i} must be uint8 [H, W] or [H, W, C], not {t.dtype} {list(t.shape)}")
+            t = t.unsqueeze(-1) if t.dim() == 2 else t
+            if t.shape[2] not in (1, 3) or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f"RaggedImageSet: image {i} must be a non-empty image of 1 or 3 channels, not {list(t.shape)}")
+            if ts and t.shape[2] != ts[0].shape[2]:
+                raise ValueError(f"RaggedImageSet: mixed channel counts (image 0 has {ts[0].shape[2]}, image {i} has {t.shape[2]}); "
+                                 "convert the set to one mode first")
+            ts.append(t)
+        if not ts:
+            raise ValueError("RaggedImageSet: at least one image is needed")
+        sizes = np.array([[t.shape[0], t.shape[1]] for t in ts], dtype=np.int32)
+        offsets, total = self.layout(sizes, ts[0].shape[2])
+        arena = torch.zeros(total, dtype=torch.uint8)
+        for t, o in zip(ts, offsets):
+            arena[int(o):int(o) + t.numel()] = t.reshape(-1).cpu()
+        self._set(arena, offsets, sizes, int(ts[0].shape[2]))
+        if device is not None and torch.device(device) != self.arena.device:
+            self._set(self.arena.to(device), offsets, sizes, self.channels)
+
+    @classmethod
+    def layout(cls, sizes, channels):
+        """(int64 offsets [n], arena length) of images of `sizes` [n, 2]: each image starts at the next multiple of ALIGN"""
+        import numpy as np
+        nbytes = sizes[:, 0].astype(np.int64) * sizes[:, 1].astype(np.int64) * int(channels)
+        padded = (nbytes + cls.ALIGN - 1) // cls.ALIGN * cls.ALIGN
+        ends = np.cumsum(padded)
+        return (ends - padded).astype(np.int64), int(ends[-1]) if len(ends) else 0
+
+    def _set(self, arena, offsets_host, sizes_host, channels):
+        import numpy as np
+        self.arena, self.channels = arena, int(channels)
+        self.offsets_host = np.ascontiguousarray(offsets_host, dtype=np.int64)
+        self.sizes = np.ascontiguousarray(sizes_host, dtype=np.int32).reshape(-1, 2)
+        self.offsets = torch.from_numpy(self.offsets_host.copy()).to(arena.device)
+        self.sizes_dev = torch.from_numpy(self.sizes.copy()).to(arena.device)
+
+    @classmethod
+    def from_parts(cls, arena, offsets_host, sizes_host, channels):
+        """a set over an arena that is laid out already (what the ragged Resize returns)"""
+        self = cls.__new__(cls)
+        self._set(arena, offsets_host, sizes_host, channels)
+        return self
+
+    @classmethod
+    def from_tensor(cls, images_u8, device=None):
+        """the equal-size set of a uint8 tensor [n, H, W, C] (or [n, H, W])"""
+        import numpy as np
+        t = images_u8.unsqueeze(-1) if images_u8.dim() == 3 else images_u8
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] not in (1, 3) or 0 in t.shape:
+            raise ValueError(f"RaggedImageSet.from_tensor: a non-empty uint8 [n, H, W, C] with C = 1 or 3 is needed, not {t.dtype} "
+                             f"{list(images_u8.shape)}")
+        n, H, W, C = t.shape
+        sizes = np.tile(np.array([[H, W]], dtype=np.int32), (n, 1))
+        offsets, total = cls.layout(sizes, C)
+        dev = t.device if device is None else torch.device(device)
+        arena = torch.zeros((n, total // n), dtype=torch.uint8, device=dev)
+        arena[:, :H * W * C] = t.reshape(n, -1).to(dev)
+        return cls.from_parts(arena.reshape(-1), offsets, sizes, C)
+
+    def to(self, device):
+        if torch.device(device) == self.arena.device:
+            return self
+        return RaggedImageSet.from_parts(self.arena.to(device), self.offsets_host, self.sizes, self.channels)
+
+    @property
+    def device(self):
+        return self.arena.device
+
+    @property
+    def is_cuda(self):
+        return self.arena.is_cuda
+
+    def __len__(self):
+        return int(self.sizes.shape[0])
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not -len(self) <= i < len(self):
+            raise IndexError(f"image {i} of a set of {len(self)}")
+        (H, W), o = self.sizes[i], int(self.offsets_host[i])
+        return self.arena[o:o + int(H) * int(W) * self.channels].view(int(H), int(W), self.channels)
+
+    @property
+    def is_uniform(self):
+        return bool((self.sizes == self.sizes[0]).all())
+
+    def as_tensor(self):
+        """uint8 [n, H, W, C] of an equal-size set (a copy); a set of mixed sizes has no such tensor"""
+        if not self.is_uniform:
+            raise ValueError("RaggedImageSet.as_tensor: the images differ in size (Resize them to one (h, w), or crop them)")
+        n, (H, W) = len(self), (int(v) for v in self.sizes[0])
+        return self.arena.view(n, -1)[:, :H * W * self.channels].reshape(n, H, W, self.channels).contiguous()
+
+
+def _ragged_args(who, src, params):
+    if not (src.is_cuda and params.is_cuda):
+        raise RuntimeError(f"{who} needs GPU tensors (there is no CPU fallback)")
+    assert params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == 4 and params.is_contiguous()
+    return (src.arena.data_ptr(), src.offsets.data_ptr(), src.sizes_dev.data_ptr(), len(src))
+
+
 def augment_batch(src_u8, params, out_hw, mean=None, std=None, flip_first=True, noise_std=0.001, seed=0):
     """gather + RandomCrop(zero padding) + RandomHorizontalFlip + ToTensor + noise + Normalize in ONE kernel over a uint8
     NHWC image set resident in HBM (`eoe_augment_batch_c`, include/eoe_hip.h): replaces the PIL transform chain of
     `main/train_cifar.py:31-38` / `main/train_clip_imagenet.py:27-36` / `main/train_fmnist.py:31-38` (after its Grayscale) and the
     Normalize of `ad_trainer.py:413-425`.
     src_u8 uint8 [n_src,Hs,Ws,C] (GPU), C = 1 or 3; params int32 [n,4] = (index, top, left, flip) (GPU) -> fp32 NCHW [n,C,Ho,Wo];
-    mean / std hold C values"""
+    mean / std hold C values.  A `RaggedImageSet` takes `eoe_ragged_augment_batch`: top / left are relative to image `index`'s own
+    extents; the result is what this function gives on that image alone, bit for bit (n = 0: an empty batch, no launch)."""
     import ctypes as C                                  # noqa: F401
     from ._lib import check, lib
+    if isinstance(src_u8, RaggedImageSet):
+        args = _ragged_args("augment_batch", src_u8, params)
+        ch, n, (Ho, Wo), dev = src_u8.channels, params.shape[0], out_hw, src_u8.device
+        m = torch.as_tensor(mean, dtype=torch.float32, device=dev).contiguous() if mean is not None else None
+        s = torch.as_tensor(std, dtype=torch.float32, device=dev).contiguous() if std is not None else None
+        for name, t in (("mean", m), ("std", s)):
+            if t is not None and t.numel() != ch:
+                raise ValueError(f"augment_batch: {name} must hold one value per channel ({ch}), not {t.numel()}")
+        out = torch.empty((n, ch, Ho, Wo), dtype=torch.float32, device=dev)
+        if n:
+            check(lib.eoe_ragged_augment_batch(*args, ch, params.data_ptr(), None if m is None else m.data_ptr(),
+                                               None if s is None else s.data_ptr(), out.data_ptr(), n, Ho, Wo, 1 if flip_first else 0,
+                                               float(noise_std), int(seed), torch.cuda.current_stream().cuda_stream),
+                  "eoe_ragged_augment_batch")
+        return out
     if not (src_u8.is_cuda and params.is_cuda):
         raise RuntimeError("augment_batch needs GPU tensors (there is no CPU fallback)")
     assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
@@ -143,8 +297,16 @@ def augment_batch(src_u8, params, out_hw, mean=None, std=None, flip_first=True, 
 def crop_flip_u8(src_u8, params, out_hw, flip_first=True):
     """the crop / flip of augment_batch alone (`eoe_crop_flip_u8_c`: same params, zero padding, both flip orders): uint8 NHWC
     [n, Ho, Wo, C] (C = 1 or 3, as the set), the PIL image the reference's uint8 transforms see between RandomCrop /
-    RandomHorizontalFlip and ToTensor"""
+    RandomHorizontalFlip and ToTensor.  A `RaggedImageSet` takes `eoe_ragged_crop_flip_u8` (origins relative to each image)."""
     from ._lib import check, lib
+    if isinstance(src_u8, RaggedImageSet):
+        args = _ragged_args("crop_flip_u8", src_u8, params)
+        n, (Ho, Wo) = params.shape[0], out_hw
+        out = torch.empty((n, Ho, Wo, src_u8.channels), dtype=torch.uint8, device=src_u8.device)
+        if n:
+            check(lib.eoe_ragged_crop_flip_u8(*args, src_u8.channels, params.data_ptr(), out.data_ptr(), n, Ho, Wo,
+                                              1 if flip_first else 0, torch.cuda.current_stream().cuda_stream), "eoe_ragged_crop_flip_u8")
+        return out
     if not (src_u8.is_cuda and params.is_cuda):
         raise RuntimeError("crop_flip_u8 needs GPU tensors (there is no CPU fallback)")
     assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
@@ -178,8 +340,8 @@ def grayscale_u8(src_u8):
     return out
 
 
-def _resize_tables(in_size, out_size, filt, device):
-    """Pillow's filter taps for one axis from the library's host helper, uploaded once"""
+def _resize_tables_host(in_size, out_size, filt):
+    """Pillow's filter taps for one axis from the library's host helper (double precision, the exact part)"""
     import ctypes as C
     from ._lib import check, lib
     k = C.c_int(0)
@@ -187,15 +349,127 @@ def _resize_tables(in_size, out_size, filt, device):
     bounds = torch.empty((out_size, 2), dtype=torch.int32)
     kk = torch.empty((out_size, k.value), dtype=torch.int32)
     check(lib.eoe_resize_coeffs(in_size, out_size, filt, bounds.data_ptr(), kk.data_ptr(), k.value, None), "eoe_resize_coeffs")
-    return bounds.to(device), kk.to(device), k.value
+    return bounds, kk, k.value
+
+
+def _resize_tables(in_size, out_size, filt, device):
+    """the same, uploaded once"""
+    bounds, kk, ks = _resize_tables_host(in_size, out_size, filt)
+    return bounds.to(device), kk.to(device), ks
+
+
+class _TapArena:
+    """the tap tables of a ragged Resize in ONE int32 array: `eoe_resize_coeffs` runs once per distinct (in, out) of the set -- a
+    few hundred for a real set, not once per image -- and an image's pass names its tables by their positions in the array"""
+
+    def __init__(self, filt, tables=_resize_tables_host):
+        self.filt, self.tables, self.at, self.chunks, self.seen = filt, tables, 0, [], {}
+
+    def entry(self, in_size, out_size):
+        """(position of bounds, position of kk, ksize); (0, 0, 0) for a pass Pillow skips"""
+        key = (int(in_size), int(out_size))
+        if key[0] == key[1]:
+            return 0, 0, 0
+        if key not in self.seen:
+            bounds, kk, ks = self.tables(key[0], key[1], self.filt)
+            self.seen[key] = (self.at, self.at + bounds.numel(), ks)
+            self.chunks += [bounds.reshape(-1), kk.reshape(-1)]
+            self.at += bounds.numel() + kk.numel()
+        return self.seen[key]
+
+    def tensor(self):
+        if self.at >= 1 << 31:
+            raise ValueError("resize_u8: the tap tables of this set exceed 2^31 entries")
+        return torch.cat(self.chunks) if self.chunks else torch.zeros(1, dtype=torch.int32)
+
+
+def ragged_resize_plan(sizes, channels, size, taps, src_offsets, packed_out):
+    """the launch geometry of a ragged Resize, on the host (numpy): per image the shapes after the horizontal and after the
+    vertical pass (Pillow's order), where each intermediate and each result starts, and the per-axis descriptor rows
+    (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, 0) of `eoe_ragged_resize_pass_u8`.
+    packed_out: the results lie back to back without gaps (the [n, h, w, C] tensor of a pair `size`), else at ALIGN-ed starts.
+    Returns dict(out_sizes, mid_offsets, mid_bytes, out_offsets, out_bytes, h=(offs, desc, max_bytes) | None, v=... | None):
+    a pass is None only when it is the identity for EVERY image; otherwise its identity images are copied by the kernel."""
+    import numpy as np
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    n, C = len(sizes), int(channels)
+    out_sizes = np.array([resized_hw(h, w, size) for h, w in sizes], dtype=np.int64).reshape(-1, 2)
+    if (out_sizes < 1).any():
+        i = int(np.argmax((out_sizes < 1).any(axis=1)))
+        raise ValueError(f"resize_u8: image {i} of {tuple(sizes[i])} would become {tuple(out_sizes[i])}")
+    H, W, Ho, Wo = sizes[:, 0], sizes[:, 1], out_sizes[:, 0], out_sizes[:, 1]
+    need_h, need_v = bool((W != Wo).any()), bool((H != Ho).any())
+    mid_sizes = np.stack([H, Wo], axis=1)
+    mid_offsets, mid_bytes = RaggedImageSet.layout(mid_sizes, C)
+    if packed_out:
+        nb = Ho * Wo * C
+        out_offsets, out_bytes = np.cumsum(nb) - nb, int(nb.sum())
+    else:
+        out_offsets, out_bytes = RaggedImageSet.layout(out_sizes, C)
+    src_offsets = np.asarray(src_offsets, dtype=np.int64)
+
+    def axis_pass(src_off, dst_off, outer, a_in, a_out, inner):
+        ent = {}
+        for pair in set(zip(a_in.tolist(), a_out.tolist())):
+            ent[pair] = taps.entry(*pair)
+        e = np.array([ent[p] for p in zip(a_in.tolist(), a_out.tolist())], dtype=np.int64).reshape(-1, 3)
+        desc = np.stack([outer, a_in, a_out, inner, e[:, 0], e[:, 1], e[:, 2], np.zeros(n, dtype=np.int64)], axis=1)
+        if desc.max() >= 1 << 31:
+            raise ValueError("resize_u8: an image of this set is too large for the pass descriptors (2^31)")
+        return (np.ascontiguousarray(np.stack([src_off, dst_off], axis=1).astype(np.int64)), np.ascontiguousarray(desc.astype(np.int32)),
+                int((outer * a_out * inner).max()))
+
+    ones, cs = np.ones(n, dtype=np.int64), np.full(n, C, dtype=np.int64)
+    plan = dict(out_sizes=out_sizes.astype(np.int32), mid_offsets=mid_offsets, mid_bytes=mid_bytes, out_offsets=out_offsets.astype(np.int64),
+                out_bytes=out_bytes, h=None, v=None)
+    if need_h:                                           # [H, W, C] -> [H, Wo, C]: into the scratch when a vertical pass follows
+        plan["h"] = axis_pass(src_offsets, mid_offsets if need_v else plan["out_offsets"], H, W, Wo, cs)
+    if need_v:                                           # [H, Wo, C] -> [Ho, Wo, C], the row is `inner`
+        plan["v"] = axis_pass(mid_offsets if need_h else src_offsets, plan["out_offsets"], ones, H, Ho, Wo * C)
+    return plan
+
+
+def _resize_ragged(rs, size, filt):
+    from ._lib import check, lib
+    if not rs.is_cuda:
+        raise RuntimeError("resize_u8 needs the set on a GPU (there is no CPU fallback)")
+    pair = not isinstance(size, int)
+    taps = _TapArena(filt)
+    plan = ragged_resize_plan(rs.sizes, rs.channels, size, taps, rs.offsets_host, pair)
+    n, C, dev = len(rs), rs.channels, rs.device
+    if plan["h"] is None and plan["v"] is None:          # Resize leaves every image as it is
+        return rs.as_tensor() if pair else rs
+    st = torch.cuda.current_stream().cuda_stream
+    out = torch.zeros(plan["out_bytes"], dtype=torch.uint8, device=dev)        # zeros: the gaps between aligned starts
+    taps_dev = taps.tensor().to(dev)
+    mid = torch.empty(plan["mid_bytes"], dtype=torch.uint8, device=dev) if plan["h"] and plan["v"] else None     # freed on return
+    cur = rs.arena
+    for name in ("h", "v"):
+        if plan[name] is None:
+            continue
+        offs, desc, biggest = plan[name]
+        dst = mid if (name == "h" and plan["v"] is not None) else out
+        offs_d, desc_d = torch.from_numpy(offs).to(dev), torch.from_numpy(desc).to(dev)
+        check(lib.eoe_ragged_resize_pass_u8(cur.data_ptr(), dst.data_ptr(), offs_d.data_ptr(), desc_d.data_ptr(), taps_dev.data_ptr(), n,
+                                            biggest, st), "eoe_ragged_resize_pass_u8")
+        cur = dst
+    if pair:
+        h, w = plan["out_sizes"][0]
+        return out.view(n, int(h), int(w), C)
+    return RaggedImageSet.from_parts(out, plan["out_offsets"], plan["out_sizes"], C)
 
 
 def resize_u8(src_u8, size, interpolation="bilinear"):
     """`torchvision.transforms.Resize(size)` as the reference applies it to PIL images (`main/train_imagenet.py:31`,
     `main/train_clip_imagenet.py:28`; bicubic for CLIP's preprocessing, `clip_official/clip/clip.py:60`), on a uint8 NHWC image
     set in HBM and byte-exact with Pillow: `size` = (h, w), or an int = the shorter side (the other int(size * long / short)).
-    Deterministic, so a resident dataset is resized ONCE, not per step."""
+    Deterministic, so a resident dataset is resized ONCE, not per step.
+    A `RaggedImageSet` is resized image by image under the same rule (`resized_hw`), all images in one launch per pass
+    (`eoe_ragged_resize_pass_u8`): an int gives a new RaggedImageSet (256 x W' or H' x 256 per image), a pair the plain tensor
+    [n, h, w, C] -- how `Resize((256, 256))` of `main/train_clip_imagenet.py:28` turns a raw mixed set into the tensor path."""
     from ._lib import check, lib, EOE_RESIZE_BILINEAR, EOE_RESIZE_BICUBIC
+    if isinstance(src_u8, RaggedImageSet):
+        return _resize_ragged(src_u8, size, {"bilinear": EOE_RESIZE_BILINEAR, "bicubic": EOE_RESIZE_BICUBIC}[interpolation])
     if not src_u8.is_cuda:
         raise RuntimeError("resize_u8 needs a GPU tensor (there is no CPU fallback)")
     assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()
@@ -241,6 +515,32 @@ def color_jitter_u8(src_u8, idx, factors, order):
     scratch = torch.empty(n, dtype=torch.int32, device=dev)
     check(lib.eoe_color_jitter_u8(src_u8.data_ptr(), src_u8.shape[0], idx.data_ptr(), factors.data_ptr(), order.data_ptr(),
                                   scratch.data_ptr(), out.data_ptr(), n, H, W, torch.cuda.current_stream().cuda_stream), "eoe_color_jitter_u8")
+    return out
+
+
+def color_jitter_crop_u8(src, params, out_hw, factors, order, flip_first=True):
+    """ColorJitter of the WHOLE image params[slot, 0] of a `RaggedImageSet` (3 channels), then the crop / flip of `crop_flip_u8`
+    with the same params -> uint8 [n, Ho, Wo, 3], equal byte for byte to `color_jitter_u8` on that image followed by `crop_flip_u8`
+    (`eoe_ragged_color_jitter_crop_u8`).  The jittered whole image is never written: the contrast op needs the rounded gray mean of
+    the whole image as it stands in front of that op, every op is pointwise once it is known, so one pass sums over the slot's
+    image and the second jitters only the pixels under the crop window.  The zero padding stays 0 (RandomCrop pads after the
+    jitter).  factors fp32 [n, 4], order int32 [n, 4] as `color_jitter_u8` takes them."""
+    from ._lib import check, lib
+    if not isinstance(src, RaggedImageSet):
+        raise TypeError("color_jitter_crop_u8 works on a RaggedImageSet (a tensor set takes color_jitter_u8, then crop_flip_u8)")
+    if src.channels != 3:
+        raise ValueError(f"color_jitter_crop_u8: images must have 3 channels, not {src.channels} (the ops are defined on RGB)")
+    args = _ragged_args("color_jitter_crop_u8", src, params)
+    dev, n, (Ho, Wo) = src.device, params.shape[0], out_hw
+    factors = factors.to(device=dev, dtype=torch.float32).contiguous()
+    order = order.to(device=dev, dtype=torch.int32).contiguous()
+    assert factors.shape == (n, 4) and order.shape == (n, 4)
+    out = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=dev)
+    if n:
+        scratch = torch.empty(n, dtype=torch.int32, device=dev)
+        check(lib.eoe_ragged_color_jitter_crop_u8(*args, params.data_ptr(), factors.data_ptr(), order.data_ptr(), scratch.data_ptr(),
+                                                  out.data_ptr(), n, Ho, Wo, 1 if flip_first else 0,
+                                                  torch.cuda.current_stream().cuda_stream), "eoe_ragged_color_jitter_crop_u8")
     return out
 
 
@@ -333,6 +633,46 @@ def gray_set(images_u8, device):
     return grayscale_u8(t) if t.shape[3] == 3 else t
 
 
+def _resident(t, device):
+    """an image set as the source keeps it: on the device; a tensor contiguous, a RaggedImageSet as packed"""
+    return t.to(device) if isinstance(t, RaggedImageSet) else t.to(device).contiguous()
+
+
+def _check_crop_fits(what, rs, crop, padding):
+    """RandomCrop(crop, padding) on a ragged set fails in torchvision for an image that is smaller than the crop after padding
+    ("Required crop size ... is larger than input image size ..."): found here, once, not in some later step"""
+    small = ((rs.sizes + 2 * int(padding)) < int(crop)).any(axis=1)
+    if small.any():
+        i = int(small.argmax())
+        h, w = (int(v) for v in rs.sizes[i])
+        raise ValueError(f"required crop size ({crop}, {crop}) is larger than {what} image {i} of size ({h}, {w}) after Resize"
+                         + (f" and padding {padding}" if padding else "") + f" ({int(small.sum())} such image(s) in the set)")
+
+
+def center_origins(sizes, crop):
+    """torchvision's CenterCrop origin per image and axis, int64 [n, 2]: int(round((H - crop) / 2.0)) (Python's round: halves to
+    even), and for an image smaller than the crop the origin its symmetric zero padding implies, -((crop - H) // 2)"""
+    import numpy as np
+    d = np.asarray(sizes, dtype=np.int64) - int(crop)
+    return np.where(d >= 0, np.rint(d / 2.0).astype(np.int64), -((-d) // 2))
+
+
+def ragged_crop_origins(sizes, crop, padding, generator=None):
+    """RandomCrop(crop, padding) origins for images of `sizes` (int [n, 2]), relative to each UNPADDED image, int64 [n, 2] =
+    (top, left): per image uniform over its own legal origins [-padding, H_i + padding - crop] (W likewise).  ONE vectorised draw per
+    coordinate, all tops first, then all lefts: u = torch.rand(n, float64) from the generator, origin = -padding + floor(u * k_i)
+    with k_i = H_i + 2 * padding - crop + 1 the number of legal origins (every origin has probability 1 / k_i up to 2^-53)."""
+    hw = torch.as_tensor(sizes, dtype=torch.int64).reshape(-1, 2)
+    k = hw + 2 * int(padding) - int(crop) + 1
+    if len(k) and int(k.min()) < 1:
+        raise ValueError("ragged_crop_origins: an image is smaller than the crop after padding")
+    cols = []
+    for a in (0, 1):
+        u = torch.rand(len(k), generator=generator, dtype=torch.float64)
+        cols.append(torch.minimum((u * k[:, a].to(torch.float64)).floor().to(torch.int64), k[:, a] - 1) - int(padding))
+    return torch.stack(cols, dim=1)
+
+
 class ResidentImageSource:
     """step-batch source whose uint8 images live in HBM: every step batch ([normal half | OE half], the BalancedConcatLoader
     contract of `datasets/bases.py:570-600`) is gathered, cropped, flipped, noised and normalised by one kernel; the host only
@@ -371,7 +711,23 @@ class ResidentImageSource:
     square, and are built one at a time while the loader is iterated.  Where the stage is the identity -- a 3-channel set whose
     crop (test images: whose size) is n_px already -- the path without the option runs, bit for bit.  Only square crops of at
     most 64 px and upsampling to at most 256 px are built; `normalize=` / `ds_statistics=` (statistics fitted on the set) and a
-    pre-tensor sharpen MSM are refused with it."""
+    pre-tensor sharpen MSM are refused with it.
+
+    Each of `normal_u8`, `oe_u8`, `test_u8` may be a `RaggedImageSet` -- images of mixed sizes, the chains of
+    `main/train_imagenet.py:30-41` (Resize(256) -> ColorJitter -> RandomCrop(224) -> flip; test: Resize(256) -> CenterCrop(224)),
+    `train_cub.py`, `train_dtd.py`, `train_mvtec.py`, `train_custom.py` -- independently of the other two:
+      * `resize=` / `test_resize=` run the ragged Resize once; an int keeps every image's aspect ratio;
+      * a crop origin is drawn per sample over THAT image's legal origins (`ragged_crop_origins`: one vectorised draw for the tops,
+        one for the lefts, then the flips, where the tensor path has its three draws; the tensor path's draws are unchanged); an
+        image smaller than the crop after Resize and padding is a ValueError here, at construction;
+      * with `color_jitter` a ragged half takes `color_jitter_crop_u8` and then `augment_batch` with identity params (the shape of
+        the sharpen path); the jitter draws and their place in the draw order are those of the tensor path;
+      * test batches are CenterCrop(crop) per image at torchvision's origin (`center_origins`);
+      * `normalize=` fits over the uint8 tensor Resize -> CenterCrop(crop) of the normal rows, as the reference does
+        (`datasets/imagenet.py:89-93, 273-278`), with the unchanged `fit_statistics`.  (The tensor path fits over the whole resized
+        images, which is the same thing only where the crop is the image.)
+      * `normal_index`, `set_oe_subset`, MSMs and `defer_normalize` work as on tensors: they select rows or act on the batch.
+    `clip_preprocessing` and `grayscale=True` are refused with a ragged set."""
 
     nominal_label, anomalous_label = 0, 1
 
@@ -382,6 +738,13 @@ class ResidentImageSource:
         color_jitter: (brightness, contrast, saturation, hue) of `transforms.ColorJitter`, drawn per sample per step;
         clip_preprocessing: n_px of CLIP's transform inside the chain (the class docstring)"""
         dev = torch.device(device)
+        if any(isinstance(t, RaggedImageSet) for t in (normal_u8, oe_u8, test_u8)):
+            if clip_preprocessing is not None:
+                raise NotImplementedError("clip_preprocessing on a RaggedImageSet is not built: its upsample kernel takes square crops "
+                                          "of one small set; Resize the set to one (h, w) first (resize_u8 with a pair gives the tensor)")
+            if grayscale:
+                raise NotImplementedError("grayscale=True on a RaggedImageSet is not built: convert the images to one channel before "
+                                          "packing them (a 1-channel RaggedImageSet is accepted)")
         if clip_preprocessing is not None:
             if normalize is not None or ds_statistics is not None:
                 raise ValueError("clip_preprocessing normalises with CLIP's own (or the given three-valued) mean / std, as "
@@ -402,7 +765,7 @@ class ResidentImageSource:
         if grayscale:
             self.normal, self.oe, self.test = (gray_set(t, dev) for t in (normal_u8, oe_u8, test_u8))
         else:
-            self.normal, self.oe, self.test = (t.to(dev).contiguous() for t in (normal_u8, oe_u8, test_u8))
+            self.normal, self.oe, self.test = (_resident(t, dev) for t in (normal_u8, oe_u8, test_u8))
         self.grayscale, self.flip = bool(grayscale), bool(flip)
         if resize is not None:
             self.normal, self.oe = resize_u8(self.normal, resize, interpolation), resize_u8(self.oe, resize, interpolation)
@@ -411,6 +774,11 @@ class ResidentImageSource:
         self.color_jitter = color_jitter
         self.test_y = test_labels.clone()
         self.crop, self.padding, self.mean, self.std = int(crop), int(padding), mean, std
+        if color_jitter is not None and any(isinstance(t, RaggedImageSet) and t.channels != 3 for t in (self.normal, self.oe)):
+            raise ValueError("color_jitter works on RGB images; a 1-channel RaggedImageSet cannot take it")
+        for what, t in (("normal", self.normal), ("OE", self.oe)):
+            if isinstance(t, RaggedImageSet):
+                _check_crop_fits(what, t, self.crop, self.padding)
         self.flip_first, self.noise_std, self.seed = flip_first, noise_std, int(seed)
         self.clip_preprocessing = None if clip_preprocessing is None else int(clip_preprocessing)
         if self.clip_preprocessing is not None:
@@ -448,8 +816,8 @@ class ResidentImageSource:
         idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int64)
         if idx.numel() == 0:
             raise ValueError("an OE subset needs at least one row (None restores the full set)")
-        if int(idx.min()) < 0 or int(idx.max()) >= self.oe.shape[0]:
-            raise IndexError(f"OE subset names rows outside the resident OE set of {self.oe.shape[0]} images")
+        if int(idx.min()) < 0 or int(idx.max()) >= len(self.oe):
+            raise IndexError(f"OE subset names rows outside the resident OE set of {len(self.oe)} images")
         self.oe_subset = idx
 
     def _resolve_normalize(self, normalize, ds_statistics):
@@ -461,6 +829,10 @@ class ResidentImageSource:
         mode = _norm.norm_mode(normalize)
         if ds_statistics is not None:
             stats = _norm.check_ds_statistics(ds_statistics, mode)
+        elif isinstance(self.normal, RaggedImageSet):
+            # the reference's fit: Resize -> CenterCrop(crop) of the normal training images (datasets/imagenet.py:89-93, 273-278)
+            rows = self.normal_index if self.normal_index is not None else torch.arange(len(self.normal))
+            stats = _norm.fit_statistics(self._center_crops(self.normal, rows), None, normalize)
         else:
             stats = _norm.fit_statistics(self.normal, self.normal_index, normalize)
         self.ds_statistics = stats
@@ -488,7 +860,7 @@ class ResidentImageSource:
         claimed MSMs, which the trainer then leaves out of the step batch's apply_msms; test batches (centre crops, no noise)
         stay with apply_msms."""
         self._pre_msms = [m for m in msms if m.transform_str == "sharpen" and m.ds_part_str in ("train_nominal", "train_oe")]
-        if self._pre_msms and self._clip_px(self.crop, self.normal.shape[3]) is not None:
+        if self._pre_msms and self.clip_preprocessing is not None and self._clip_px(self.crop, self.normal.shape[3]) is not None:
             self._pre_msms = []
             raise NotImplementedError("a train sharpen MSM works on the uint8 crop in front of clip_preprocessing's upsample; that "
                                       "combination is not built")
@@ -500,15 +872,20 @@ class ResidentImageSource:
         px = self.clip_preprocessing
         return None if px is None or (side == px and channels == 3) else px
 
-    def _augment_half(self, src, p, nominal, mean, std, seed):
-        """one half of a step batch: augment_batch, or with claimed sharpen MSMs for this half the reference's order"""
+    def _augment_half(self, src, p, nominal, mean, std, seed, jitter=None):
+        """one half of a step batch: augment_batch, or with claimed sharpen MSMs for this half the reference's order.
+        jitter: (factors, order) of a ragged half under color_jitter -- ColorJitter and the crop / flip are then one uint8 stage
+        (`color_jitter_crop_u8`) in front of the sharpen MSMs and of augment_batch with identity params"""
         ops = [m for m in getattr(self, "_pre_msms", ()) if (m.ds_part_str == "train_nominal") == nominal]
-        if self._clip_px(self.crop, src.shape[3]) is not None:               # a sharpen MSM is refused together with it (pre_tensor_msms)
+        if self.clip_preprocessing is not None and self._clip_px(self.crop, src.shape[3]) is not None:   # a sharpen MSM is refused together with it (pre_tensor_msms)
             return augment_resize_batch(src, p, self.crop, self.clip_preprocessing, mean, std, self.flip_first, self.noise_std, seed)
-        if not ops or p.shape[0] == 0:
+        if (not ops and jitter is None) or p.shape[0] == 0:
             return augment_batch(src, p, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, seed)
         from .msm import sharpen_percent, sharpen_u8
-        u8 = crop_flip_u8(src, p, (self.crop, self.crop), self.flip_first)
+        if jitter is not None:
+            u8 = color_jitter_crop_u8(src, p, (self.crop, self.crop), jitter[0], jitter[1], self.flip_first)
+        else:
+            u8 = crop_flip_u8(src, p, (self.crop, self.crop), self.flip_first)
         for m in ops:
             if m.magnitude is None:
                 raise ValueError(f"MSM {m} has no magnitude set")
@@ -525,10 +902,30 @@ class ResidentImageSource:
         flip = torch.randint(0, 2, (n,), generator=self._g) if self.flip else torch.zeros(n, dtype=torch.int64)
         return torch.stack([idx.to(torch.int64), top, left, flip], dim=1).to(torch.int32)
 
+    def _params_ragged(self, idx, sizes):
+        """_params for rows `idx` of a ragged set with the host table `sizes`: the origins of `ragged_crop_origins` (tops, then
+        lefts), then the flips as the tensor path draws them"""
+        idx = idx.to(torch.int64)
+        tl = ragged_crop_origins(torch.from_numpy(sizes)[idx], self.crop, self.padding, self._g)
+        flip = torch.randint(0, 2, (len(idx),), generator=self._g) if self.flip else torch.zeros(len(idx), dtype=torch.int64)
+        return torch.stack([idx, tl[:, 0], tl[:, 1], flip], dim=1).to(torch.int32)
+
+    def _draw(self, idx, src):
+        if isinstance(src, RaggedImageSet):
+            return self._params_ragged(idx, src.sizes)
+        return self._params(idx, src.shape[1], src.shape[2])
+
+    def _center_crops(self, src, rows):
+        """uint8 [len(rows), crop, crop, C]: CenterCrop(crop) of the listed images of a ragged set"""
+        rows = torch.as_tensor(rows, dtype=torch.int64)
+        tl = torch.from_numpy(center_origins(src.sizes[rows.numpy()], self.crop))
+        p = torch.stack([rows, tl[:, 0], tl[:, 1], torch.zeros_like(rows)], dim=1).to(torch.int32).to(src.device)
+        return crop_flip_u8(src, p, (self.crop, self.crop), True)
+
     def _epoch(self, batch_size):
-        subset = self.normal_index if self.normal_index is not None else torch.arange(self.normal.shape[0])
-        oe_rows = self.oe_subset if self.oe_subset is not None else torch.arange(self.oe.shape[0])
-        n, n_full, m = len(subset), self.normal.shape[0], len(oe_rows)
+        subset = self.normal_index if self.normal_index is not None else torch.arange(len(self.normal))
+        oe_rows = self.oe_subset if self.oe_subset is not None else torch.arange(len(self.oe))
+        n, n_full, m = len(subset), len(self.normal), len(oe_rows)
         perm = subset[torch.randperm(n, generator=self._g)]
         oe_idx = tile_oe_indices(oe_rows, n)
         if m >= 10000:                                   # bases.py:561: OE sets of >= 10 000 samples are drawn with replacement
@@ -541,21 +938,29 @@ class ResidentImageSource:
             oi = oe_order[s:s + batch_size][:len(ni)]            # the OE half is cut to the normal half's size (bases.py:597)
             self._step += 1
             # two launches (normal half from its image set, OE half from the other), written into one batch tensor
-            pn = self._params(ni, self.normal.shape[1], self.normal.shape[2]).to(dev)
-            po = self._params(oi, self.oe.shape[1], self.oe.shape[2]).to(dev)
+            pn = self._draw(ni, self.normal).to(dev)
+            po = self._draw(oi, self.oe).to(dev)
             seed = (self.seed * 65521 + self._step) % (1 << 23)
-            src_n, src_o = self.normal, self.oe
+            src_n, src_o, jit_n, jit_o = self.normal, self.oe, None, None
             if self.color_jitter is not None:
                 # ColorJitter comes first in the reference's chains (train_cifar.py:32, train_clip_imagenet.py:29): the gathered,
                 # jittered uint8 images become the "set" the crop / flip kernel reads (slot i = image i)
                 fn, on = sample_color_jitter(len(ni), *self.color_jitter, generator=self._g)
                 fo, oo = sample_color_jitter(len(oi), *self.color_jitter, generator=self._g)
-                src_n, src_o = color_jitter_u8(self.normal, ni, fn, on), color_jitter_u8(self.oe, oi, fo, oo)
-                pn[:, 0] = torch.arange(len(ni), dtype=torch.int32, device=dev)
-                po[:, 0] = torch.arange(len(oi), dtype=torch.int32, device=dev)
+                # a ragged half keeps its set and its indices: the jitter runs under the crop window (_augment_half)
+                if isinstance(self.normal, RaggedImageSet):
+                    jit_n = (fn, on)
+                else:
+                    src_n = color_jitter_u8(self.normal, ni, fn, on)
+                    pn[:, 0] = torch.arange(len(ni), dtype=torch.int32, device=dev)
+                if isinstance(self.oe, RaggedImageSet):
+                    jit_o = (fo, oo)
+                else:
+                    src_o = color_jitter_u8(self.oe, oi, fo, oo)
+                    po[:, 0] = torch.arange(len(oi), dtype=torch.int32, device=dev)
             mean, std = self._norm_args()
-            xn = self._augment_half(src_n, pn, True, mean, std, 2 * seed)
-            xo = self._augment_half(src_o, po, False, mean, std, 2 * seed + 1)
+            xn = self._augment_half(src_n, pn, True, mean, std, 2 * seed, jit_n)
+            xo = self._augment_half(src_o, po, False, mean, std, 2 * seed + 1, jit_o)
             lbls = torch.cat([torch.full((len(ni),), self.nominal_label, dtype=torch.int64),
                               torch.full((len(oi),), self.anomalous_label, dtype=torch.int64)])
             yield torch.cat([xn, xo]), lbls, torch.cat([ni, oi + n_full])      # OE indices offset by the FULL normal set (bases.py:596)
@@ -568,10 +973,10 @@ class ResidentImageSource:
                 return outer._epoch(batch_size)
 
             def __len__(s):
-                n = outer.normal.shape[0] if outer.normal_index is None else len(outer.normal_index)
+                n = len(outer.normal) if outer.normal_index is None else len(outer.normal_index)
                 return math.ceil(n / batch_size)
 
-        if self._clip_px(self.test.shape[1], self.test.shape[3]) is not None:
+        if self.clip_preprocessing is not None and self._clip_px(self.test.shape[1], self.test.shape[3]) is not None:
             # CLIP's transform on the raw test images (val_transform is empty, training/clip.py:44-46): the same kernel with an
             # identity "crop" of the whole image, no noise; 224 x 224 x 3 floats per image, so a batch exists only while it is used
             class _Test:
@@ -589,8 +994,15 @@ class ResidentImageSource:
 
             return _Train(), _Test()
         # test split: centre crop, no flip, no noise (val_transform: ToTensor + normalize, train_cifar.py:39-42)
-        Hs, Ws = self.test.shape[1], self.test.shape[2]
         test = []
+        if isinstance(self.test, RaggedImageSet):        # CenterCrop(crop) of each image at its own origin (train_imagenet.py:38-41)
+            tl = torch.from_numpy(center_origins(self.test.sizes, self.crop))
+            for s in range(0, len(self.test_y), batch_size):
+                idx = torch.arange(s, min(s + batch_size, len(self.test_y)))
+                p = torch.stack([idx, tl[idx, 0], tl[idx, 1], torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
+                test.append((augment_batch(self.test, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx))
+            return _Train(), test
+        Hs, Ws = self.test.shape[1], self.test.shape[2]
         for s in range(0, len(self.test_y), batch_size):
             idx = torch.arange(s, min(s + batch_size, len(self.test_y)))
             p = torch.stack([idx, torch.full_like(idx, (Hs - self.crop) // 2), torch.full_like(idx, (Ws - self.crop) // 2),
@@ -637,13 +1049,16 @@ class LabelledImageSet:
         grayscale: the 1-channel chain of `ResidentImageSource(grayscale=True)`; colour sets are converted here, once for all
         tasks.  `flip=False` and the other options of the source go through `source_kw`."""
         dev = torch.device(device)
+        if grayscale and any(isinstance(t, RaggedImageSet) for t in (train_u8, test_u8, oe_u8)):
+            raise NotImplementedError("grayscale=True on a RaggedImageSet is not built: convert the images to one channel before "
+                                      "packing them (a 1-channel RaggedImageSet is accepted)")
         if grayscale:
             if source_kw.get("color_jitter") is not None:
                 raise ValueError("color_jitter works on RGB images and cannot be combined with grayscale=True")
             self.train, self.test, self.oe = (gray_set(t, dev) for t in (train_u8, test_u8, oe_u8))
             source_kw = dict(source_kw, grayscale=True)
         else:
-            self.train, self.test, self.oe = (t.to(dev).contiguous() for t in (train_u8, test_u8, oe_u8))
+            self.train, self.test, self.oe = (_resident(t, dev) for t in (train_u8, test_u8, oe_u8))
         self.train_classes = torch.as_tensor(train_classes, dtype=torch.int64).clone()
         self.test_classes = torch.as_tensor(test_classes, dtype=torch.int64).clone()
         self.classes = list(classes)

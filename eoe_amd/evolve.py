@@ -41,6 +41,10 @@ class OEPool:
     with the same results) and `valid_indices`, the rows an id may name (`evolve/__init__.py:42-52`; default: all rows)"""
 
     def __init__(self, oe_u8: torch.Tensor, valid_indices=None):
+        from .data import RaggedImageSet
+        if isinstance(oe_u8, RaggedImageSet):
+            raise NotImplementedError("the candidate search measures distances between OE images of ONE shape; a RaggedImageSet has "
+                                      "none (Resize the pool to one (h, w) first: resize_u8 with a pair gives the tensor)")
         if oe_u8.dtype != torch.uint8 or oe_u8.dim() < 2:
             raise ValueError("OEPool needs a uint8 image set [n, ...]")
         self.images = oe_u8.contiguous()

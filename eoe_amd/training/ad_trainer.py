@@ -177,7 +177,7 @@ class ADTrainer(ABC):
             raise NotImplementedError(f"oe_limit_samples needs a source whose OE set can be restricted (set_oe_subset); "
                                       f"{type(ds).__name__} has none")
         if isinstance(limit, (int, float)):
-            n = int(ds.oe.shape[0])
+            n = len(ds.oe)                          # a tensor or a RaggedImageSet: rows of the resident OE set
             rows = sorted(np.random.choice(n, min(int(limit), n), False))
         else:
             rows = list(limit)

@@ -903,6 +903,36 @@ int eoe_grayscale_u8(const uint8_t* src, uint8_t* dst, int64_t n_pixels, void* s
 int eoe_augment_resize_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, int C, const int32_t* params, int crop_h, int crop_w,
                              int n_px, int filter, const int32_t* bounds, const int32_t* kk, const float* mean, const float* std,
                              float* out, int n, int flip_first, float noise_std, uint64_t seed, void* stream);
+/* Image sets of MIXED sizes (main/train_imagenet.py:30-34, train_cub.py, train_dtd.py, train_mvtec.py, train_custom.py: Resize(256)
+ * with an int keeps the aspect ratio, so after it every image has its own shape).  A ragged set is
+ *   arena   uint8, the images back to back, each row-major HWC with C = 1 or 3 for the whole set; no row is assumed aligned
+ *   offsets int64 [n_src], the byte at which image i starts;   sizes int32 [n_src, 2] = (H_i, W_i)
+ * all three on the device.  params / out / flip_first / noise / mean / std are those of the functions above, and the results are
+ * equal to theirs bit for bit on each image taken as a 1-image set; a slot whose index lies outside [0, n_src) is all padding.
+ * n == 0 returns 0 without a launch.
+ *   eoe_ragged_augment_batch         eoe_augment_batch_c: fp32 NCHW [n, C, Ho, Wo]
+ *   eoe_ragged_crop_flip_u8          eoe_crop_flip_u8_c: uint8 [n, Ho, Wo, C]
+ *   eoe_ragged_color_jitter_crop_u8  eoe_color_jitter_u8 of image params[slot][0] as a whole (C = 3), THEN eoe_crop_flip_u8 of it,
+ *                                    uint8 [n, Ho, Wo, 3], without writing the jittered image: one pass sums the gray level in
+ *                                    front of the contrast op over the slot's whole image into gray_mean_scratch (int32 [n]), the
+ *                                    second applies the ops under the crop window only; the padding stays 0
+ *   eoe_ragged_resize_pass_u8        eoe_resize_pass_u8 for every image of a set in one launch: image i is src + offs[2 i] as
+ *                                    [outer, axis_in, inner] -> dst + offs[2 i + 1] as [outer, axis_out, inner] (offs int64 [n, 2]),
+ *                                    desc int32 [n, 8] = (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, 0) where
+ *                                    bounds_at / kk_at are positions in `taps`, an int32 array holding the eoe_resize_coeffs
+ *                                    tables (ksize_cap = ksize) of every distinct (in, out) of the set; an image with axis_in ==
+ *                                    axis_out is copied (Pillow skips that pass).  max_out_bytes: the largest image's output,
+ *                                    which sizes the launch.  All arrays on the device; the taps are computed on the host. */
+int eoe_ragged_augment_batch(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C,
+                             const int32_t* params, const float* mean, const float* std, float* out, int n, int Ho, int Wo,
+                             int flip_first, float noise_std, uint64_t seed, void* stream);
+int eoe_ragged_crop_flip_u8(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C,
+                            const int32_t* params, uint8_t* out, int n, int Ho, int Wo, int flip_first, void* stream);
+int eoe_ragged_color_jitter_crop_u8(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src,
+                                    const int32_t* params, const float* factors, const int32_t* order, int32_t* gray_mean_scratch,
+                                    uint8_t* out, int n, int Ho, int Wo, int flip_first, void* stream);
+int eoe_ragged_resize_pass_u8(const uint8_t* src, uint8_t* dst, const int64_t* offs, const int32_t* desc, const int32_t* taps, int n,
+                              int64_t max_out_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
