@@ -250,6 +250,8 @@ SIGNATURES = {
     "eoe_gcn_normalize": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "eoe_pool_sqdist_workspace": [_i64, C.c_int, C.c_int, C.POINTER(_sz)],
     "eoe_pool_sqdist_u8": [_vp, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp],
+    "eoe_pool_sqdist_ragged_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_sz)],
+    "eoe_pool_sqdist_ragged_u8": [_vp, _i64, _vp, _vp, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp],
     "eoe_pool_rank": [_vp, C.c_int, C.c_int, _vp, _vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],

@@ -10,6 +10,13 @@ the host dataset one at a time and measures their squared distance to the parent
 mated individual; here the images already sit in HBM as uint8 and `OEPool.distances` is a gather, one distance kernel and one
 rank kernel (`csrc/evolve.hip`), with one small copy back.
 
+A pool of MIXED sizes (`RaggedImageSet`: the 224 x 224 tasks after `Resize(256)`, `main/evolve_oe_imagenet.py`,
+`main/evolve_oe_custom.py`) is searched without resizing anything to a common shape: `OEPool(rs, crop=224)` or
+`OEPool.from_source(src)` compares each image's `CenterCrop(crop)` window -- the stored-bytes analogue there, the window the test
+split scores and `normalize=` fits over, zero-padded for an image smaller than the crop -- with `eoe_pool_sqdist_ragged_u8`, which
+reads the windows straight out of the arena.  `run_evolution(trainer, OEPool.from_source(trainer.ds), ...)` runs such a search; the
+default `pool=None` keeps refusing a ragged OE set, since it cannot know the window.
+
 What differs from the reference, deliberately:
   * Distances are taken on the STORED images (after the source's one-time resize), as exact integers.  The reference's
     `oeds[id][0]` passes every image through the random train transform (jitter, crop, flip, noise) each time it is fetched, so
@@ -37,23 +44,43 @@ RANK_MAX_CANDIDATES = 1024                # eoe_pool_rank
 
 # --------------------------------------------------------------------------------------------------------------- the pool
 class OEPool:
-    """the complete OE set the search draws from: uint8 images [n, H, W, C] (a GPU tensor: the kernels; a CPU tensor: numpy int64
-    with the same results) and `valid_indices`, the rows an id may name (`evolve/__init__.py:42-52`; default: all rows)"""
+    """the complete OE set the search draws from and `valid_indices`, the rows an id may name (`evolve/__init__.py:42-52`; default:
+    all rows).  The set is uint8 images [n, H, W, C] (a GPU tensor: the kernels; a CPU tensor: numpy int64 with the same results),
+    compared whole, or a `RaggedImageSet` with `crop=` (an int or (h, w)): images of mixed sizes have no common shape, so what is
+    compared is each image's `CenterCrop(crop)` window, zero-padded where the image is smaller (`data.center_origins`)"""
 
-    def __init__(self, oe_u8: torch.Tensor, valid_indices=None):
-        from .data import RaggedImageSet
+    def __init__(self, oe_u8, valid_indices=None, crop=None):
+        from .data import RaggedImageSet, center_origins
+        self.crop = self._origins = None
         if isinstance(oe_u8, RaggedImageSet):
-            raise NotImplementedError("the candidate search measures distances between OE images of ONE shape; a RaggedImageSet has "
-                                      "none (Resize the pool to one (h, w) first: resize_u8 with a pair gives the tensor)")
-        if oe_u8.dtype != torch.uint8 or oe_u8.dim() < 2:
-            raise ValueError("OEPool needs a uint8 image set [n, ...]")
-        self.images = oe_u8.contiguous()
-        n = self.images.shape[0]
+            if crop is None:
+                raise NotImplementedError("the candidate search measures distances between OE images of ONE shape; a RaggedImageSet has "
+                                          "none (pass crop=: the CenterCrop(crop) windows are compared, OEPool.from_source takes the "
+                                          "source's; or Resize the pool to one (h, w) first: resize_u8 with a pair gives the tensor)")
+            ch, cw = (int(crop), int(crop)) if isinstance(crop, (int, np.integer)) else (int(v) for v in crop)
+            if ch < 1 or cw < 1:
+                raise ValueError(f"OEPool: crop must be positive, not {crop}")
+            self.images, self.crop = oe_u8, (ch, cw)
+            n, self.features = len(oe_u8), ch * cw * oe_u8.channels
+            self._origins = np.stack([center_origins(oe_u8.sizes[:, 0], ch), center_origins(oe_u8.sizes[:, 1], cw)], axis=1).astype(np.int32)
+        else:
+            if crop is not None:
+                raise ValueError("OEPool: crop= selects the windows of a RaggedImageSet; a tensor set is compared whole")
+            if oe_u8.dtype != torch.uint8 or oe_u8.dim() < 2:
+                raise ValueError("OEPool needs a uint8 image set [n, ...]")
+            self.images = oe_u8.contiguous()
+            n, self.features = self.images.shape[0], int(np.prod(self.images.shape[1:]))
         self.valid_indices = np.arange(n, dtype=np.int64) if valid_indices is None else np.asarray(valid_indices, dtype=np.int64).reshape(-1)
         if len(self.valid_indices) == 0 or self.valid_indices.min() < 0 or self.valid_indices.max() >= n:
             raise ValueError(f"valid_indices must name rows of the set of {n} images, and at least one")
-        self.features = int(np.prod(self.images.shape[1:]))
         self._workspace = None
+
+    @classmethod
+    def from_source(cls, src, valid_indices=None):
+        """the pool of a source's resident OE set (`ResidentImageSource.oe`): a tensor set as it is, a ragged one with the source's
+        crop -- the window its test split scores and `normalize=` fits over"""
+        from .data import RaggedImageSet
+        return cls(src.oe, valid_indices, crop=src.crop if isinstance(src.oe, RaggedImageSet) else None)
 
     def __len__(self) -> int:
         return len(self.valid_indices)
@@ -66,24 +93,43 @@ class OEPool:
         return self.valid_indices[ids]
 
     def distances(self, query_ids, cand_ids) -> Tuple[np.ndarray, np.ndarray]:
-        """squared distances of every query image to every candidate image, on the stored bytes: (int64 [K, P], int32 [K, P]) =
-        (the distances, per query the stable ascending order of them as positions in `cand_ids`), both on the host"""
+        """squared distances of every query image to every candidate image, on the stored bytes (a ragged set: on the centre
+        windows): (int64 [K, P], int32 [K, P]) = (the distances, per query the stable ascending order of them as positions in
+        `cand_ids`), both on the host"""
         q, c = self.rows(query_ids).astype(np.int32), self.rows(cand_ids).astype(np.int32)
         if len(q) < 1 or len(c) < 1:
             raise ValueError("distances need at least one query and one candidate")
         if self.images.is_cuda:
             return self._distances_device(q, c)
-        flat = self.images.reshape(self.images.shape[0], -1).numpy()
-        qi, ci = flat[q].astype(np.int64), flat[c].astype(np.int64)
+        if self.crop is not None:
+            flat = self._windows_host(np.concatenate([q, c])).reshape(len(q) + len(c), -1).astype(np.int64)
+            qi, ci = flat[:len(q)], flat[len(q):]
+        else:
+            flat = self.images.reshape(self.images.shape[0], -1).numpy()
+            qi, ci = flat[q].astype(np.int64), flat[c].astype(np.int64)
         dist = np.stack([((ci - row) ** 2).sum(axis=1) for row in qi])
         return dist, np.argsort(dist, axis=1, kind="stable").astype(np.int32)
+
+    def _windows_host(self, rows) -> np.ndarray:
+        """uint8 [len(rows), crop_h, crop_w, C]: the centre windows of the listed images of a CPU ragged set, zero-padded"""
+        (ch, cw), out = self.crop, np.zeros((len(rows), *self.crop, self.images.channels), dtype=np.uint8)
+        for i, r in enumerate(rows):
+            img, (top, left) = self.images[int(r)].numpy(), (int(v) for v in self._origins[r])
+            H, W = img.shape[:2]
+            y0, y1, x0, x1 = max(top, 0), min(top + ch, H), max(left, 0), min(left + cw, W)
+            out[i, y0 - top:y1 - top, x0 - left:x1 - left] = img[y0:y1, x0:x1]
+        return out
 
     def _distances_device(self, q: np.ndarray, c: np.ndarray):
         import ctypes
         from ._lib import check, lib
         K, P, dev = len(q), len(c), self.images.device
         need = ctypes.c_size_t(0)
-        check(lib.eoe_pool_sqdist_workspace(self.features, K, P, ctypes.byref(need)), "eoe_pool_sqdist_workspace")
+        if self.crop is not None:
+            check(lib.eoe_pool_sqdist_ragged_workspace(*self.crop, self.images.channels, K, P, ctypes.byref(need)),
+                  "eoe_pool_sqdist_ragged_workspace")
+        else:
+            check(lib.eoe_pool_sqdist_workspace(self.features, K, P, ctypes.byref(need)), "eoe_pool_sqdist_workspace")
         if self._workspace is None or self._workspace.numel() < need.value:
             self._workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
         # distances and order in ONE buffer (K * P int64, then K * P int32), so that both come back in one copy
@@ -92,10 +138,20 @@ class OEPool:
         q, c = np.ascontiguousarray(q), np.ascontiguousarray(c)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            check(lib.eoe_pool_sqdist_u8(self.images.data_ptr(), self.images.shape[0], self.features, q.ctypes.data, K, c.ctypes.data, P,
-                                         dist.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream), "eoe_pool_sqdist_u8")
+            if self.crop is not None:
+                # (row, top, left) of the queries, then of the candidates, in ONE array: the entry point uploads it in one copy
+                rows, win = np.concatenate([q, c]), np.empty((K + P, 3), dtype=np.int32)
+                win[:, 0], win[:, 1:] = rows, self._origins[rows]
+                rs = self.images
+                check(lib.eoe_pool_sqdist_ragged_u8(rs.arena.data_ptr(), rs.arena.numel(), rs.offsets.data_ptr(), rs.sizes_dev.data_ptr(),
+                                                    len(rs), rs.channels, *self.crop, win.ctypes.data, K, win[K:].ctypes.data, P,
+                                                    dist.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream),
+                      "eoe_pool_sqdist_ragged_u8")
+            else:
+                check(lib.eoe_pool_sqdist_u8(self.images.data_ptr(), self.images.shape[0], self.features, q.ctypes.data, K, c.ctypes.data, P,
+                                             dist.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream), "eoe_pool_sqdist_u8")
             check(lib.eoe_pool_rank(dist.data_ptr(), K, P, order.data_ptr(), stream), "eoe_pool_rank")
-            host = out.cpu().numpy()             # synchronises: the index arrays q, c were alive for the whole call
+            host = out.cpu().numpy()             # synchronises: the index arrays q, c (win) were alive for the whole call
         return host[:K * P * 8].view(np.int64).reshape(K, P).copy(), host[K * P * 8:].view(np.int32).reshape(K, P).copy()
 
 
@@ -378,7 +434,8 @@ def run_evolution(trainer, pool: Optional[OEPool], classes: Sequence[int], itera
                   mutation_chance: float = 0.5, mate_chance: float = 0.2, generations: int = 30, select_toursize: int = 3,
                   minimize_fitness: bool = False, fitness_fn: Callable = None, random_pick: bool = False) -> dict:
     """the evolve experiment (`main/evolve_oe_cifar.py:82-103`; `random_pick`: `main/random_oe_cifar.py:76-82`) with the
-    reference's defaults.  `pool`: the OE images the ids name (None: the resident OE set of the trainer's source).  `fitness_fn`
+    reference's defaults.  `pool`: the OE images the ids name (None: the resident OE set of the trainer's source, which must be a
+    tensor; for a ragged one pass `OEPool.from_source(trainer.ds)`).  `fitness_fn`
     (individual -> float) replaces the default, the mean test AUC of `trainer.run(classes, iterations)` on the individual's OE
     images; with it no trainer is needed (`trainer` may be None).  Returns the history; it is also written as
     `evolve_results.json` (the trainer's own `results.json` of the last training lies next to it), and the genealogy (node id,

@@ -635,6 +635,18 @@ int eoe_gcn_normalize(const float* x, float* y, int n, int C, int H, int W, int 
  *                        (chunks of 1 KiB .. 64 KiB, about 1 024 workgroups); a chunk sums in 32 bits, chunks are added in 64 bits
  *                        by a second small launch (no atomics; integer sums, so bitwise repeatable either way).  D % 16 != 0
  *                        takes a byte-wise path.  workspace: eoe_pool_sqdist_workspace(D, K, P) bytes, 16-byte aligned.
+ *   eoe_pool_sqdist_ragged_u8   the same sum for a set of MIXED sizes (arena / offsets / sizes / n_set / C: the ragged set of
+ *                        eoe_ragged_crop_flip_u8 below; arena_bytes: its length; the arena starts at and is as long as a multiple of
+ *                        16 bytes), over a crop_h x crop_w x C window of each listed image:
+ *                        out[k][p] = sum (window(query[k]) - window(cand[p]))^2.  query [K][3] / cand [P][3] are HOST int32 arrays of
+ *                        (row, top, left), the origin relative to the row's own unpadded image; window bytes outside the image count
+ *                        as 0 (any origin is allowed: every window row and column is checked against the device `sizes`, and an
+ *                        image whose extent does not lie in the arena counts as empty).  Rows are checked against n_set, K <= 1024,
+ *                        P <= 2^20 and 1 <= crop_h * crop_w * C <= 2^26 before anything is copied or launched (EOE_ERR_ARG).  Chunks,
+ *                        32-bit partial sums and the 64-bit second pass are those of eoe_pool_sqdist_u8: no atomics, bitwise
+ *                        repeatable.  Window rows are not aligned; no load leaves [arena, arena + arena_bytes).  Lists that lie back
+ *                        to back on the host (cand == query + 3 K) are uploaded in one copy; they must stay valid until the stream
+ *                        has passed the call.  workspace: eoe_pool_sqdist_ragged_workspace(...) bytes, 16-byte aligned.
  *   eoe_pool_rank        order[k][.] = the stable ascending order of dist[k][.] as positions 0 .. P-1 (equal distances keep list
  *                        order: the `arg` of torch's stable sort), int32 [K][P], DEVICE; dist int64 [K][P].  One launch, rank by
  *                        counting in LDS.  P <= 1024, larger P is EOE_ERR_UNSUPPORTED.
@@ -642,6 +654,10 @@ int eoe_gcn_normalize(const float* x, float* y, int n, int C, int H, int W, int 
 int eoe_pool_sqdist_workspace(int64_t D, int K, int P, size_t* bytes_out);
 int eoe_pool_sqdist_u8(const uint8_t* set, int64_t n_set, int64_t D, const int32_t* query_idx, int K, const int32_t* cand_idx, int P,
                        int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+int eoe_pool_sqdist_ragged_workspace(int crop_h, int crop_w, int C, int K, int P, size_t* bytes_out);
+int eoe_pool_sqdist_ragged_u8(const uint8_t* arena, int64_t arena_bytes, const int64_t* offsets, const int32_t* sizes, int64_t n_set,
+                              int C, int crop_h, int crop_w, const int32_t* query, int K, const int32_t* cand, int P, int64_t* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
 int eoe_pool_rank(const int64_t* dist, int K, int P, int32_t* order, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
