@@ -22,7 +22,9 @@ from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .graph import GraphedStep          # noqa: F401
 from .normalize import fit_statistics, gcn_normalize, GlobalContrastNormalization, GcnNormalize  # noqa: F401
 from .evolve import OEPool, run_evolution  # noqa: F401
+from .imgrid import image_grid           # noqa: F401
 
 __all__ = ["set_compute_dtype", "compute_dtype", "hsc_loss", "hsc_score", "bce_loss", "bce_score", "linear",
            "FusedAdam", "FusedSGD", "GraphedStep", "set_parity_mode", "parity_mode", "set_grad_scale", "grad_scale",
-           "default_grad_scale", "fit_statistics", "gcn_normalize", "GlobalContrastNormalization", "GcnNormalize", "OEPool", "run_evolution"]
+           "default_grad_scale", "fit_statistics", "gcn_normalize", "GlobalContrastNormalization", "GcnNormalize", "OEPool", "run_evolution",
+           "image_grid"]

@@ -253,6 +253,9 @@ SIGNATURES = {
     "eoe_pool_sqdist_ragged_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_sz)],
     "eoe_pool_sqdist_ragged_u8": [_vp, _i64, _vp, _vp, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp],
     "eoe_pool_rank": [_vp, C.c_int, C.c_int, _vp, _vp],
+    "eoe_grid_f32": [_vp, _i64] + [C.c_int] * 3 + [_vp] + [C.c_int] * 8 + [_vp, _vp, _i64, _vp],
+    "eoe_grid_u8": [_vp, _i64] + [C.c_int] * 3 + [_vp] + [C.c_int] * 8 + [_vp, _vp, _i64, _vp],
+    "eoe_grid_ragged_u8": [_vp, _i64, _vp, _vp, _i64] + [C.c_int] * 3 + [_vp] + [C.c_int] * 8 + [_vp, _vp, _i64, _vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
     "eoe_comm_destroy": [_vp],

@@ -994,21 +994,59 @@ class ResidentImageSource:
 
             return _Train(), _Test()
         # test split: centre crop, no flip, no noise (val_transform: ToTensor + normalize, train_cifar.py:39-42)
-        test = []
-        if isinstance(self.test, RaggedImageSet):        # CenterCrop(crop) of each image at its own origin (train_imagenet.py:38-41)
+        return _Train(), [self._test_batch(idx) for idx in self._test_index_batches(batch_size)]
+
+    def _test_index_batches(self, batch_size):
+        return (torch.arange(s, min(s + batch_size, len(self.test_y))) for s in range(0, len(self.test_y), batch_size))
+
+    def _test_batch(self, idx):
+        """(images, labels, indices) of the listed test rows (no clip_preprocessing): CenterCrop(crop) of each image -- a ragged set:
+        at its own origin (train_imagenet.py:38-41, `center_origins`)"""
+        if isinstance(self.test, RaggedImageSet):
             tl = torch.from_numpy(center_origins(self.test.sizes, self.crop))
-            for s in range(0, len(self.test_y), batch_size):
-                idx = torch.arange(s, min(s + batch_size, len(self.test_y)))
-                p = torch.stack([idx, tl[idx, 0], tl[idx, 1], torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
-                test.append((augment_batch(self.test, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx))
-            return _Train(), test
-        Hs, Ws = self.test.shape[1], self.test.shape[2]
-        for s in range(0, len(self.test_y), batch_size):
-            idx = torch.arange(s, min(s + batch_size, len(self.test_y)))
+            p = torch.stack([idx, tl[idx, 0], tl[idx, 1], torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
+        else:
+            Hs, Ws = self.test.shape[1], self.test.shape[2]
             p = torch.stack([idx, torch.full_like(idx, (Hs - self.crop) // 2), torch.full_like(idx, (Ws - self.crop) // 2),
                              torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
-            test.append((augment_batch(self.test, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx))
-        return _Train(), test
+        return augment_batch(self.test, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx
+
+    PREVIEW_SEED = 0x9E3779B1
+
+    def preview(self, percls=40, train=True):
+        """`TorchvisionDataset.preview` (`bases.py:246-291`): (fp32 NCHW tensor, {label: count}) = the first `percls` images per label
+        of the loader's output taken in batches of 10, label 0 first, cut to the rarest label's number, and how many samples of each
+        label the split holds (`n_normal_anomalous`: the row headers of the preview figure).  Train batches are drawn from a PRIVATE
+        generator (seeded from the source's seed) with the step counter put back afterwards: asking for a preview leaves the
+        source's own random state, and so every later batch, unchanged.  Test batches are built only as far as needed."""
+        if train:
+            n_normal = len(self.normal) if self.normal_index is None else len(self.normal_index)
+            counts = {self.nominal_label: n_normal, self.anomalous_label: len(self.oe) if self.oe_subset is None else len(self.oe_subset)}
+        else:
+            labels, numbers = torch.unique(self.test_y, return_counts=True)
+            counts = {int(k): int(v) for k, v in zip(labels.tolist(), numbers.tolist())}
+        kept = self._g, self._step
+        self._g = torch.Generator().manual_seed((self.seed + self.PREVIEW_SEED) % (1 << 63))
+        try:
+            if train:
+                batches = self._epoch(10)
+            elif self.clip_preprocessing is not None and self._clip_px(self.test.shape[1], self.test.shape[3]) is not None:
+                batches = iter(self.loaders(10)[1])
+            else:
+                batches = (self._test_batch(idx) for idx in self._test_index_batches(10))
+            xs, ys = [], []
+            for xb, yb, _ in batches:
+                xs.append(xb)
+                ys.append(yb)
+                y = torch.cat(ys)
+                if all(int((y == c).sum()) >= percls for c in counts):
+                    break
+        finally:
+            self._g, self._step = kept
+        x, y = torch.cat(xs), torch.cat(ys).to(xs[0].device)
+        out = [x[y == c][:percls] for c in sorted(set(y.tolist()))]
+        percls = min(o.shape[0] for o in out)
+        return torch.cat([o[:percls] for o in out]), counts
 
 
 def normal_subset(class_labels, normal_classes) -> torch.Tensor:

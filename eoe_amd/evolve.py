@@ -29,8 +29,19 @@ What differs from the reference, deliberately:
   * `evaluate` trains only the individuals whose fitness is unset (the reference's `ind in invalid_ind` compares id lists, so a
     valid twin of an invalid individual is trained again); `history['pop']` holds a copy of each generation's id lists (the
     reference appends the one population object it keeps overwriting).
-  * Out of scope: the genealogy plots and PNG grids (`logimg`, `imsave_collection_best`), `--ev-continue-run`, CLI runners.
+  * The figures (`run_evolution(log_images=True)`; `evolve/__init__.py:209-240, 278-355`, `evolve/tree.py:262-340`) are composed on
+    the device from (pool, ids) by `logger.logimg` -> `eoe_amd.imgrid.image_grid`: no image tensor is built on the host, where the
+    reference fetches every image through the dataset (and its random train transform) again for each figure.  They show the
+    STORED images (a ragged pool: the centre windows the distances are taken on).  The sorted `gen{g}` grid orders whole
+    individuals by fitness (stable); the reference zips the fitness list with the flat image list, which pairs -- and keeps -- only
+    the first `len(pop)` images once an individual holds more than one.  The "best / worst k" figures compose the chosen
+    individuals' strips again from the pool (one launch pair for all k) rather than re-reading their PNG files; the second pass
+    normalises the first pass's bytes, as the reference's does.  `mark`'s frame colours and the other stated differences of the
+    pictures themselves: `eoe_amd/imgrid.py`.
+  * Out of scope: `Tree.vis` (the graphviz genealogy plot), the `final-transformed` MSM figures, text drawn into pictures (row
+    headers go to `<name>.headers.json`), `--ev-continue-run`, the CLI runners.
 """
+import os
 import random
 from copy import deepcopy
 from typing import Callable, List, Optional, Sequence, Tuple
@@ -214,11 +225,52 @@ class Genealogy:
         ind.node = len(self.nodes) - 1
         return ind.node
 
-    def evaluated(self, ind: Individual, gen: int, fitness: float):
+    def evaluated(self, ind: Individual, gen: int, fitness: float, file: str = None):
+        """`file`: the path of the individual's picture (`node.content.file`, `evolve/__init__.py:219`); the key exists only on
+        nodes whose picture was logged"""
         self.nodes[ind.node].update(generation=int(gen), fitness=float(fitness), ids=[int(i) for i in ind])
+        if file is not None:
+            self.nodes[ind.node]["file"] = file
 
     def to_json(self) -> list:
         return deepcopy(self.nodes)
+
+    def scores_best(self, k: int = 20, reverse: bool = False, return_nodes: bool = False):
+        """the fitness values of the k best evaluated individuals, ascending (`reverse`: of the k worst), as `tree.py:262-281`:
+        nodes with a fitness, sorted by id list (stable) with repeats of an id list dropped (the first one is kept), then sorted by
+        fitness (stable), then the last k (`reverse`: the first k).  `return_nodes`: (values, nodes).  Nodes are visited in the
+        order of their creation where the reference walks its tree breadth-first; the two differ only in which of several nodes
+        with EQUAL id lists, or in which order nodes of EQUAL fitness, are kept."""
+        nodes = sorted((n for n in self.nodes if n["fitness"] is not None), key=lambda n: n["ids"])
+        nodes = [n for i, n in enumerate(nodes) if i == 0 or n["ids"] != nodes[i - 1]["ids"]]
+        nodes = sorted(nodes, key=lambda n: n["fitness"])
+        nodes = (nodes[:k] if reverse else nodes[-k:]) if k > 0 else []
+        fits = [n["fitness"] for n in nodes]
+        return (fits, nodes) if return_nodes else fits
+
+    def imsave_best(self, logger, pool: "OEPool", name: str, k: int = 20, reverse: bool = False, print_fitness: bool = False):
+        """`tree.py:283-320`: one figure of the k best (`reverse`: worst) individuals.  Each individual's strip -- the picture of its
+        `individuals/...` file, `nrow=16` -- is composed on the device, all k strips by ONE launch pair into one buffer; the strips
+        are then composed again as uint8 cells with `maxres=1024`: side by side (`nrow=k`), or one per row with the fitness values as
+        `rowheaders` (`print_fitness`).  The reference re-reads the PNG files and normalises a second time; here the second pass
+        takes the first pass's bytes.  Returns the picture (None when nothing was evaluated)."""
+        from .imgrid import image_grids
+        fits, nodes = self.scores_best(k, reverse, return_nodes=True)
+        if not nodes:
+            return None
+        if len({len(n["ids"]) for n in nodes}) != 1:
+            raise ValueError("imsave_best: the individuals differ in their number of OE images; their strips have no common shape")
+        strips = image_grids(pool, [n["ids"] for n in nodes], nrow=16)
+        if print_fitness:
+            return logger.logimg(name, strips, nrow=1, rowheaders=[f"{f * 100:06.3f}" for f in fits], maxres=1024)
+        return logger.logimg(name, strips, nrow=k, maxres=1024)
+
+    def imsave_collection_best(self, logger, pool: "OEPool", k: int = 20):
+        """`tree.py:322-340` without the MSM figures: `final/best_raw`, `final/best`, `final/worst_raw`, `final/worst`"""
+        self.imsave_best(logger, pool, os.path.join("final", "best_raw"), k=k)
+        self.imsave_best(logger, pool, os.path.join("final", "best"), k=k, print_fitness=True)
+        self.imsave_best(logger, pool, os.path.join("final", "worst_raw"), k=k, reverse=True)
+        self.imsave_best(logger, pool, os.path.join("final", "worst"), k=k, reverse=True, print_fitness=True)
 
 
 # --------------------------------------------------------------------------------------------------------------- operators
@@ -349,9 +401,33 @@ def rand_pick_setup(oesize: int, generation_pool: int, pool: OEPool, evaluate_fn
     return pop, 0, toolbox, history, tree
 
 
-def evaluate(offspring: list, pop: list, gen: int, toolbox: Toolbox, history: dict, tree: Genealogy, logger=None):
+def _flat_ids(individuals) -> list:
+    return [int(i) for ind in individuals for i in ind]
+
+
+def _stage_figure(logger, pool: OEPool, name: str, before: list, after: list, groups: list, flat: bool = False):
+    """a selection / mating / mutation figure (`evolve/__init__.py:278-355`): the id lists `before` over the id lists `after`, one
+    individual per row (one image each: all in one row) with 16 black rows between the two, and every group of individuals in
+    `groups` (positions in before + after) framed in a colour of its own.  `flat` is the selection figure's rule for several
+    images per individual (:285): ONE flat list of cells, so that every cell takes the next colour"""
+    size = len(before[0])
+    if size > 1:
+        nrow, row_sep_at = size, (16, len(before))
+        mark = [[j for i in group for j in range(i * size, (i + 1) * size)] for group in groups]
+        mark = [j for group in mark for j in group] if flat else mark
+    else:
+        nrow, row_sep_at, mark = len(before), (16, 1), groups
+    return logger.logimg(name, pool, _flat_ids(before) + _flat_ids(after), nrow=nrow, row_sep_at=row_sep_at, mark=mark)
+
+
+def evaluate(offspring: list, pop: list, gen: int, toolbox: Toolbox, history: dict, tree: Genealogy, logger=None, pool: OEPool = None,
+             log_images: bool = False):
     """`evolve/__init__.py:188-249`: train every offspring whose fitness is unset, make the offspring the population and append
-    the generation's statistics to the history"""
+    the generation's statistics to the history.  `log_images` (needs `logger` and `pool`): the picture of every newly evaluated
+    individual as `individuals/gen{g}_ind{i}_fit{f}` (its path goes to the individual's genealogy node), the generation as
+    `raw_gen/gen{g}` and, individuals ordered by fitness, as `gen{g}` with the fitness values as row headers"""
+    if log_images and (logger is None or pool is None):
+        raise ValueError("log_images needs a logger (logimg) and the OE pool")
     for i, ind in enumerate(offspring):
         if ind.fitness.valid:
             continue
@@ -359,9 +435,13 @@ def evaluate(offspring: list, pop: list, gen: int, toolbox: Toolbox, history: di
             logger.print(f"Evaluate ind{i:03}..")
         fit = float(toolbox.evaluate(ind))
         ind.fitness.values = (fit,)
-        tree.evaluated(ind, gen, fit)
+        name, file = f"gen{gen:03}_ind{i:03}_fit{fit * 100:06.3f}", None
+        if log_images:
+            logger.logimg(os.path.join("individuals", name), pool, list(ind), nrow=16)
+            file = os.path.join(logger.dir or "", "individuals", name + ".png")
+        tree.evaluated(ind, gen, fit, file)
         if logger is not None:
-            logger.logtxt(f"gen{gen:03}_ind{i:03}_fit{fit * 100:06.3f} with ids {list(ind)}")
+            logger.logtxt(f"{name} with ids {list(ind)}")
     pop[:] = offspring
     fits = [ind.fitness.values[0] for ind in pop]
     history["pop"].append([[int(i) for i in ind] for ind in pop])
@@ -370,6 +450,11 @@ def evaluate(offspring: list, pop: list, gen: int, toolbox: Toolbox, history: di
     history["std_fit"].append(float(np.std(fits)))
     history["min_fit"].append(float(np.min(fits)))
     history["max_fit"].append(float(np.max(fits)))
+    if log_images:
+        logger.logimg(os.path.join("raw_gen", f"gen{gen:03}"), pool, _flat_ids(pop), nrow=len(pop[0]))
+        order = sorted(range(len(pop)), key=lambda i: fits[i])
+        logger.logimg(f"gen{gen:03}", pool, _flat_ids(pop[i] for i in order), nrow=len(pop[0]),
+                      rowheaders=[f"{fits[i] * 100:06.3f}" for i in order])
     if logger is not None:
         logger.print(f"GENERATION {gen:03}")
         logger.print(f"  Min {history['min_fit'][-1] * 100:06.3f}")
@@ -379,24 +464,41 @@ def evaluate(offspring: list, pop: list, gen: int, toolbox: Toolbox, history: di
 
 
 def evolve(pop: list, gen: int, toolbox: Toolbox, mate_chance: float, mutation_chance: float, history: dict, tree: Genealogy,
-           logger=None):
+           logger=None, pool: OEPool = None, log_images: bool = False):
     """one generation (`evolve/__init__.py:252-357`): tournament survivors, neighbours mated with `mate_chance`, everyone
-    mutated with `mutation_chance` (both drawn from `random`, as there), then `evaluate`"""
+    mutated with `mutation_chance` (both drawn from `random`, as there), then `evaluate`.  `log_images`: `selection/gen{g}`,
+    `mating/gen{g}` and `mutation/gen{g}` show the population in front of and behind each stage, with the survivors, the mated
+    pairs and the mutants framed (`:278-355`); no draw depends on it"""
+    if log_images and (logger is None or pool is None):
+        raise ValueError("log_images needs a logger (logimg) and the OE pool")
+    n = len(pop)
+
+    def figure(stage, before, groups, flat=False):
+        if log_images:
+            _stage_figure(logger, pool, os.path.join(stage, f"gen{gen:03}"), before, offspring, groups, flat)
+
     offspring = [toolbox.clone(ind) for ind in toolbox.select(pop, len(pop))]
-    for child1, child2 in zip(offspring[::2], offspring[1::2]):
+    figure("selection", pop, [[i for i, ind in enumerate(pop) if ind in offspring]] if log_images else None, flat=True)
+    before, picked = [list(ind) for ind in offspring] if log_images else None, []
+    for i, (child1, child2) in enumerate(zip(offspring[::2], offspring[1::2])):
         if random.random() < mate_chance:
             parents = (child1.node, child2.node)
             toolbox.mate(child1, child2)
+            picked.append(i)
             for child in (child1, child2):
                 child.fitness.invalidate()
                 tree.add(child, parents)
-    for mutant in offspring:
+    figure("mating", before, [[p * 2, p * 2 + 1, n + p * 2, n + p * 2 + 1] for p in picked])
+    before, picked = [list(ind) for ind in offspring] if log_images else None, []
+    for i, mutant in enumerate(offspring):
         if random.random() < mutation_chance:
             parent = mutant.node
             toolbox.mutate(mutant)
+            picked.append(i)
             mutant.fitness.invalidate()
             tree.add(mutant, (parent,))
-    evaluate(offspring, pop, gen, toolbox, history, tree, logger)
+    figure("mutation", before, [[p, n + p] for p in picked])
+    evaluate(offspring, pop, gen, toolbox, history, tree, logger, pool, log_images)
 
 
 def trainer_fitness(trainer, pool: OEPool, classes: Sequence[int], iterations: int) -> Callable:
@@ -432,15 +534,24 @@ def prepare_trainer(trainer, classes: Sequence[int]):
 def run_evolution(trainer, pool: Optional[OEPool], classes: Sequence[int], iterations: int = 1, *, oesize: int = 1,
                   generation_pool: int = 16, mutation_pool: int = 100, mutation_indp: float = 1.0, mutation_oneofkbest: int = 3,
                   mutation_chance: float = 0.5, mate_chance: float = 0.2, generations: int = 30, select_toursize: int = 3,
-                  minimize_fitness: bool = False, fitness_fn: Callable = None, random_pick: bool = False) -> dict:
+                  minimize_fitness: bool = False, fitness_fn: Callable = None, random_pick: bool = False,
+                  log_images: bool = False) -> dict:
     """the evolve experiment (`main/evolve_oe_cifar.py:82-103`; `random_pick`: `main/random_oe_cifar.py:76-82`) with the
     reference's defaults.  `pool`: the OE images the ids name (None: the resident OE set of the trainer's source, which must be a
     tensor; for a ragged one pass `OEPool.from_source(trainer.ds)`).  `fitness_fn`
     (individual -> float) replaces the default, the mean test AUC of `trainer.run(classes, iterations)` on the individual's OE
     images; with it no trainer is needed (`trainer` may be None).  Returns the history; it is also written as
     `evolve_results.json` (the trainer's own `results.json` of the last training lies next to it), and the genealogy (node id,
-    generation, ids, fitness, parent ids) as `evolution.json`, through the trainer's logger."""
+    generation, ids, fitness, parent ids) as `evolution.json`, through the trainer's logger.
+
+    `log_images=True` also writes the reference's figures through `logger.logimg`, each composed on the device from (pool, ids):
+    per evaluated individual `individuals/gen{g}_ind{i}_fit{f}.png` (the path is kept on its genealogy node as `file`), per
+    generation `raw_gen/gen{g}`, `gen{g}` (sorted by fitness), `selection/`, `mating/` and `mutation/gen{g}`, and at the end
+    `final/best_raw`, `final/best`, `final/worst_raw`, `final/worst`.  Off (the default) nothing of it runs and the same files
+    are written as before."""
     logger = getattr(trainer, "logger", None)
+    if log_images and not hasattr(logger, "logimg"):
+        raise ValueError("log_images=True needs the trainer's logger to have logimg (JsonLogger)")
     if fitness_fn is None:
         ds = prepare_trainer(trainer, classes)
         if pool is None:
@@ -458,9 +569,11 @@ def run_evolution(trainer, pool: Optional[OEPool], classes: Sequence[int], itera
             oesize, generation_pool, mutation_pool, mutation_indp, mutation_oneofkbest, mutation_chance, mate_chance, generations,
             select_toursize, pool, fitness_fn, getattr(trainer, "oe_dsstr", None), not minimize_fitness)
     try:
-        evaluate(pop, pop, gen, toolbox, history, tree, logger)
+        evaluate(pop, pop, gen, toolbox, history, tree, logger, pool, log_images)
         for gen in range(1, generations):
-            evolve(pop, gen, toolbox, mate_chance, mutation_chance, history, tree, logger)
+            evolve(pop, gen, toolbox, mate_chance, mutation_chance, history, tree, logger, pool, log_images)
+        if log_images:
+            tree.imsave_collection_best(logger, pool)
     finally:
         if logger is not None:
             logger.logjson("evolve_results", history)

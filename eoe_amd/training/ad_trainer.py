@@ -80,6 +80,25 @@ class JsonLogger:
     def add_scalar(self, *a, **k):
         pass
 
+    def logimg(self, name: str, src, rows=None, nrow: int = 8, pad: int = 2, rowheaders=None, row_sep_at=(None, None),
+               maxres: int = 128, step: int = None, mark=None, crop=None) -> np.ndarray:
+        """`Logger.logimg` (`logger.py:202-295`) on images that lie where they are: `eoe_amd.imgrid.image_grid(src, rows, ...)`
+        composes the uint8 [Hg, Wg, 3] picture (on the device for a device source), one copy brings it back, and when the logger is
+        active Pillow writes it as `<dir>/<name>.png` (`<name>_v<step>.png` with `step`), sub-directories created.  Text is not
+        drawn: `rowheaders` go to `<name>.headers.json` next to the picture (a list of strings, one per grid row) and no black
+        header column is added.  Without Pillow the picture is still returned (one warning).  Always returns the array."""
+        from ..imgrid import image_grid, save_png
+        img = image_grid(src, rows, crop=crop, nrow=nrow, pad=pad, maxres=maxres, mark=mark, row_sep_at=row_sep_at).cpu().numpy()
+        if self.active:
+            stem = os.path.join(self.dir, f"{name}_v{step}" if step is not None else name)
+            os.makedirs(os.path.dirname(stem), exist_ok=True)
+            if img.size:
+                save_png(stem + ".png", img)
+            if rowheaders is not None:
+                with open(stem + ".headers.json", "w") as f:
+                    json.dump([str(h) for h in rowheaders], f)
+        return img
+
     def snapshot(self, name: str, net: torch.nn.Module, opt=None, sched=None, epoch: int = None, **kwargs):
         if not self.active:
             return None
@@ -100,7 +119,8 @@ class ADTrainer(ABC):
                  wdk: float = 0.0, milestones: List[int] = (), batch_size: int = 128, ad_mode: str = "one_vs_rest",
                  device: Union[str, torch.device] = "cuda", oe_limit_samples=np.inf, oe_limit_classes=np.inf,
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
-                 graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False):
+                 graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
+                 previews: bool = False):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -113,7 +133,14 @@ class ADTrainer(ABC):
         PRC; `ad_trainer.py:308-313`).  The reference's intermediate plots after every seed (`:283, 295-296`) draw from `np.random`
         as well whenever a class has more than one curve; those draws are NOT replayed, so from the second seed of a class on the
         generator is not where the reference's is.  With `curves=False` (the default) nothing of this runs: no extra launch, no
-        draw, the same return values and files as before."""
+        draw, the same return values and files as before.
+
+        `previews=True`: with an active logger, the first seed of a class logs `training_cls{c}-{cstr}_preview` (40 images per label of
+        the train loader's output) and `eval_cls{c}-{cstr}_preview` (20 per label of the test loader's) as the reference does
+        (`ad_trainer.py:386-393, 486-493`), through `ds.preview` and `logger.logimg`: one row per label, the labels' sample counts as
+        `rowheaders`.  The source draws the preview from a private generator, so the training that follows is unchanged.  Default
+        off: nothing runs, nothing is drawn, the same files as before."""
+        self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
         # launch-bound small encoders (CNN32 at 32x32); single GPU only, ragged batches run eagerly
@@ -369,6 +396,16 @@ class ADTrainer(ABC):
         has_bn = any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules())
         return has_bn and self.lr >= 1e-3
 
+    def _log_preview(self, ds, name: str, percls: int, train: bool, seed: int):
+        """the preview figure of a task's first seed (`ad_trainer.py:386-393, 486-493`); only with `previews=True` and an active logger"""
+        if not (self.previews and seed == 0 and self.logger.active):
+            return
+        if not hasattr(ds, "preview"):
+            raise NotImplementedError(f"previews=True needs a source with preview(); {type(ds).__name__} has none")
+        prev, stats = ds.preview(percls, train)
+        heads = [str(stats[k]) for k in sorted(stats)] if train else [f"{k}: {v}" for k, v in sorted(stats.items())]
+        self.logger.logimg(name, prev, nrow=max(prev.shape[0] // len(stats), 1), rowheaders=heads)
+
     def make_optimizer(self, model: torch.nn.Module):
         """Adam for every encoder (ad_trainer.py:383); the CLIP objective overrides this with SGD-Nesterov (:380-381)"""
         return FusedAdam(model.parameters(), lr=self.lr, weight_decay=self.wdk, amsgrad=False)
@@ -383,6 +420,7 @@ class ADTrainer(ABC):
         sched = torch.optim.lr_scheduler.MultiStepLR(opt, self.milestones, 0.1)                       # :384
         self._msm_source(ds)
         loader, _ = ds.loaders(self.batch_size, num_workers=self.workers, persistent=True)              # :385
+        self._log_preview(ds, f"training_cls{cls}-{clsstr}_preview", 40, True, seed)                      # :386-393
         ep = self.load(load if isinstance(load, str) else None, model, opt, sched)                      # :396
         center = self.center = self.prepare_metric(clsstr, loader, model, seed)                         # :397
         self._normalize_hook(model, ds)
@@ -504,6 +542,7 @@ class ADTrainer(ABC):
         model = model.to(self.device).eval()
         self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
+        self._log_preview(ds, f"eval_cls{cls}-{clsstr}_preview", 20, False, seed)                         # :486-493
         self._normalize_hook(model, ds)
         center = self.center
         nominal = getattr(ds, "nominal_label", 0)

@@ -950,6 +950,35 @@ int eoe_ragged_color_jitter_crop_u8(const uint8_t* arena, const int64_t* offsets
 int eoe_ragged_resize_pass_u8(const uint8_t* src, uint8_t* dst, const int64_t* offs, const int32_t* desc, const int32_t* taps, int n,
                               int64_t max_out_bytes, void* stream);
 
+/* Image grids composed on the device (csrc/grid.hip): the uint8 picture the reference's Logger.logimg hands to cv2.imwrite
+ * (utils/logger.py:202-295), from images that already lie in HBM.  n cells in `groups` pictures of per = n / groups cells each, back to
+ * back in `out`; one picture is uint8 [Hg + sep_height, Wg, 3]:
+ *     cell = h x w, or maxres x maxres when h > maxres or w > maxres (torch's bilinear rule, align_corners=False, no antialias)
+ *     xmaps = min(nrow, per), ymaps = ceil(per / xmaps), Hg = (ch + pad) * ymaps + pad, Wg = (cw + pad) * xmaps + pad
+ *     cell k at (pad + (k / xmaps) * (ch + pad), pad + (k % xmaps) * (cw + pad)); padding and unused cells 0; C = 1 fills 3 channels
+ *     sep_height > 0: that many black rows in front of row min((ch + pad) * sep_at + pad / 2, Hg)
+ * table  DEVICE int32 [n, 4] = (row of the source set, window top, window left, mark); a row outside [0, n_src) is an all-zero cell.
+ *        top / left are read by the ragged form only.  mark: -1, or the frame colour 0xRRGGBB (read only when `marked`).
+ * marked == 0: make_grid(normalize=True, scale_each=True) per cell over its values after the resize:
+ *        byte = trunc((clamp(x, lo, hi) - lo) / max(hi - lo, 1e-5f) * 255)
+ * marked != 0: logger.py:234-246: byte = trunc((x - lo) / (hi - lo) * 255), 0 for a constant cell, and the outermost 1-pixel frame
+ *        of a cell whose mark >= 0 is that colour.
+ * minmax DEVICE float [2 n] scratch (the per-cell min / max, left there).  out_bytes must be the pictures' size exactly.  n == 0 with
+ * out_bytes == 0 returns 0 without a launch.  EOE_ERR_ARG, naming the argument, before any launch: C not 1 or 3, nrow < 1, pad / maxres /
+ * sizes out of range, n * C * ch * cw or out_bytes at or beyond 2^31.
+ *   eoe_grid_f32        x fp32 NCHW [n_src, C, h, w]: the values as they are
+ *   eoe_grid_u8         set uint8 NHWC [n_src, H, W, C]: value = byte / 255.0f (ToTensor)
+ *   eoe_grid_ragged_u8  the crop_h x crop_w window at (top, left) of image `row` of a ragged set (arena / offsets / sizes as above),
+ *                       relative to the unpadded image; window pixels outside the image are 0 (the windows eoe_pool_sqdist_ragged_u8
+ *                       compares); an image whose extent does not lie in [0, arena_bytes) is all 0 */
+int eoe_grid_f32(const float* x, int64_t n_src, int C, int h, int w, const int32_t* table, int n, int groups, int nrow, int pad,
+                 int maxres, int sep_height, int sep_at, int marked, float* minmax, uint8_t* out, int64_t out_bytes, void* stream);
+int eoe_grid_u8(const uint8_t* set, int64_t n_src, int H, int W, int C, const int32_t* table, int n, int groups, int nrow, int pad,
+                int maxres, int sep_height, int sep_at, int marked, float* minmax, uint8_t* out, int64_t out_bytes, void* stream);
+int eoe_grid_ragged_u8(const uint8_t* arena, int64_t arena_bytes, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C,
+                       int crop_h, int crop_w, const int32_t* table, int n, int groups, int nrow, int pad, int maxres, int sep_height,
+                       int sep_at, int marked, float* minmax, uint8_t* out, int64_t out_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
  * its kernel launches with hipEvents on the stream it launches on and records the algorithmic flops / bytes.
