@@ -703,32 +703,49 @@ __global__ __launch_bounds__(256) void resize_pass_kernel(const uint8_t* __restr
 }
 
 // resize_pass_kernel over a ragged set, all images in ONE launch: image i is src + offs[2 i] viewed as [outer, axis_in, inner] ->
-// dst + offs[2 i + 1] as [outer, axis_out, inner], with desc[8 i ..] = (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, 0);
+// dst + offs[2 i + 1] as [outer, axis_out, inner], with desc[8 i ..] = (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, first);
 // bounds_at / kk_at are positions in `taps`, the int32 arena that holds the host's eoe_resize_coeffs tables, one per distinct
-// (in, out, filter) of the set.  bpi workgroups share an image's output bytes.  axis_in == axis_out: Pillow skips the pass, the
-// image is copied.  Integer arithmetic only; nothing about the taps is computed here.
+// (in, out, filter) of the set.  bpi workgroups share an image's output bytes.  Integer arithmetic only; nothing about the taps is
+// computed here.
+// `first` is a window on the output axis (CLIP's CenterCrop after its Resize): the pass writes outputs [first, first + axis_out) of the
+// full axis, packed as [outer, axis_out, inner]; bounds_at / kk_at still name the tables of the FULL axis, row `first + x` of them is
+// output x.  With first = 0 and axis_out the full axis this is the whole pass.  ksize == 0 marks the pass Pillow skips (the full
+// output axis equals axis_in; axis_in == axis_out alone cannot say so under a window): the window of the image is copied -- all of
+// it without a window.  The source offset is signed and is added to the element's position before the pointer is formed: a
+// vertical pass behind a horizontal one that wrote only the rows its taps touch is given the position source row 0 WOULD have,
+// which may lie in front of the intermediate (ragged_resize_plan); no tap of the window reads there.
 __global__ __launch_bounds__(256) void resize_pass_ragged_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                                  const long long* __restrict__ offs, const int32_t* __restrict__ desc,
                                                                  const int32_t* __restrict__ taps, int bpi) {
     const int img = blockIdx.x / bpi, part = blockIdx.x % bpi;
     const int32_t* d = desc + (size_t)img * 8;
-    const int outer = d[0], axis_in = d[1], axis_out = d[2], inner = d[3], ksize = d[6];
-    const uint8_t* s = src + offs[2 * (size_t)img];
+    const int outer = d[0], axis_in = d[1], axis_out = d[2], inner = d[3], ksize = d[6], win = d[7];
+    const long long so = offs[2 * (size_t)img];
     uint8_t* o = dst + offs[2 * (size_t)img + 1];
     const size_t total = (size_t)outer * axis_out * inner;
     const size_t first = (size_t)part * 256 + threadIdx.x, step = (size_t)bpi * 256;
-    if (axis_in == axis_out) {
-        for (size_t i = first; i < total; i += step) o[i] = s[i];
+    if (ksize == 0) {
+        if (win == 0 && axis_in == axis_out) {               // the whole image, as one run of bytes
+            const uint8_t* s = src + so;
+            for (size_t i = first; i < total; i += step) o[i] = s[i];
+            return;
+        }
+        for (size_t i = first; i < total; i += step) {
+            const int in = (int)(i % inner);
+            const int xx = (int)((i / inner) % axis_out) + win;
+            const size_t r = i / ((size_t)inner * axis_out);
+            o[i] = src[so + (long long)((r * axis_in + xx) * inner + in)];
+        }
         return;
     }
     const int32_t* bounds = taps + d[4];
     const int32_t* kk = taps + d[5];
     for (size_t i = first; i < total; i += step) {
         const int in = (int)(i % inner);
-        const int xx = (int)((i / inner) % axis_out);
+        const int xx = (int)((i / inner) % axis_out) + win;
         const size_t r = i / ((size_t)inner * axis_out);
         const int xmin = bounds[2 * xx], cnt = bounds[2 * xx + 1];
-        const uint8_t* p = s + (r * axis_in + xmin) * inner + in;
+        const uint8_t* p = src + (so + (long long)((r * axis_in + xmin) * inner + in));
         const int32_t* k = kk + (size_t)xx * ksize;
         int ss = 1 << (RESIZE_PRECISION_BITS - 1);
         for (int x = 0; x < cnt; ++x) ss += (int)p[(size_t)x * inner] * k[x];

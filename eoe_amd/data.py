@@ -363,7 +363,7 @@ class _TapArena:
     few hundred for a real set, not once per image -- and an image's pass names its tables by their positions in the array"""
 
     def __init__(self, filt, tables=_resize_tables_host):
-        self.filt, self.tables, self.at, self.chunks, self.seen = filt, tables, 0, [], {}
+        self.filt, self.tables, self.at, self.chunks, self.seen, self.bounds = filt, tables, 0, [], {}, {}
 
     def entry(self, in_size, out_size):
         """(position of bounds, position of kk, ksize); (0, 0, 0) for a pass Pillow skips"""
@@ -373,9 +373,21 @@ class _TapArena:
         if key not in self.seen:
             bounds, kk, ks = self.tables(key[0], key[1], self.filt)
             self.seen[key] = (self.at, self.at + bounds.numel(), ks)
+            self.bounds[key] = bounds.reshape(-1, 2).numpy()
             self.chunks += [bounds.reshape(-1), kk.reshape(-1)]
             self.at += bounds.numel() + kk.numel()
         return self.seen[key]
+
+    def reach(self, in_size, out_size, first, count):
+        """[lo, hi): the source positions that the taps of outputs [first, first + count) touch; an identity pass touches its own"""
+        if int(in_size) == int(out_size):
+            return int(first), int(first) + int(count)
+        self.entry(in_size, out_size)
+        b = self.bounds[(int(in_size), int(out_size))]
+        # Pillow's xmin and xmin + count never decrease with the output position (Resample.c: both follow the tap centre), so the
+        # first and the last row of the window span its union
+        last = int(first) + int(count) - 1
+        return int(b[int(first), 0]), int(b[last, 0]) + int(b[last, 1])
 
     def tensor(self):
         if self.at >= 1 << 31:
@@ -383,64 +395,82 @@ class _TapArena:
         return torch.cat(self.chunks) if self.chunks else torch.zeros(1, dtype=torch.int32)
 
 
-def ragged_resize_plan(sizes, channels, size, taps, src_offsets, packed_out):
+def ragged_resize_plan(sizes, channels, size, taps, src_offsets, packed_out, window=None):
     """the launch geometry of a ragged Resize, on the host (numpy): per image the shapes after the horizontal and after the
     vertical pass (Pillow's order), where each intermediate and each result starts, and the per-axis descriptor rows
-    (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, 0) of `eoe_ragged_resize_pass_u8`.
+    (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, first) of `eoe_ragged_resize_pass_u8`.
     packed_out: the results lie back to back without gaps (the [n, h, w, C] tensor of a pair `size`), else at ALIGN-ed starts.
-    Returns dict(out_sizes, mid_offsets, mid_bytes, out_offsets, out_bytes, h=(offs, desc, max_bytes) | None, v=... | None):
+    window: int [n, 4] = (top, left, height, width) per image, a crop of the RESIZED image (CenterCrop behind Resize): only the
+    window is computed and written.  The horizontal pass then writes columns [left, left + width) of the source rows [r0, r1) that
+    the vertical window's taps touch (`_TapArena.reach`; an image without a vertical pass: the window's own rows) into an
+    [r1 - r0, width, C] intermediate, and the vertical pass, whose tables count source rows from 0, gets the position row 0 of that
+    intermediate would have: its start minus r0 rows (possibly in front of the intermediate; no tap of the window goes below r0).
+    A window outside its resized image is a ValueError.  Without a window every `first` is 0 and the rows are what they always were.
+    Returns dict(out_sizes, mid_sizes, mid_offsets, mid_bytes, out_offsets, out_bytes, h=(offs, desc, max_bytes) | None, v=... | None):
     a pass is None only when it is the identity for EVERY image; otherwise its identity images are copied by the kernel."""
     import numpy as np
     sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
     n, C = len(sizes), int(channels)
-    out_sizes = np.array([resized_hw(h, w, size) for h, w in sizes], dtype=np.int64).reshape(-1, 2)
-    if (out_sizes < 1).any():
-        i = int(np.argmax((out_sizes < 1).any(axis=1)))
-        raise ValueError(f"resize_u8: image {i} of {tuple(sizes[i])} would become {tuple(out_sizes[i])}")
-    H, W, Ho, Wo = sizes[:, 0], sizes[:, 1], out_sizes[:, 0], out_sizes[:, 1]
-    need_h, need_v = bool((W != Wo).any()), bool((H != Ho).any())
-    mid_sizes = np.stack([H, Wo], axis=1)
+    full = np.array([resized_hw(h, w, size) for h, w in sizes], dtype=np.int64).reshape(-1, 2)
+    if (full < 1).any():
+        i = int(np.argmax((full < 1).any(axis=1)))
+        raise ValueError(f"resize_u8: image {i} of {tuple(sizes[i])} would become {tuple(full[i])}")
+    H, W, Ho, Wo = sizes[:, 0], sizes[:, 1], full[:, 0], full[:, 1]
+    zeros = np.zeros(n, dtype=np.int64)
+    if window is None:
+        top, left, wh, ww, r0, r1 = zeros, zeros, Ho, Wo, zeros, H
+    else:
+        win = np.asarray(window, dtype=np.int64).reshape(-1, 4)
+        if len(win) != n:
+            raise ValueError(f"resize_u8: {len(win)} windows for {n} images")
+        top, left, wh, ww = win[:, 0], win[:, 1], win[:, 2], win[:, 3]
+        bad = (top < 0) | (left < 0) | (wh < 1) | (ww < 1) | (top + wh > Ho) | (left + ww > Wo)
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"resize_u8: the window (top, left, height, width) = {tuple(int(v) for v in win[i])} of image {i} lies "
+                             f"outside its resized image of {tuple(int(v) for v in full[i])}")
+        reach = np.array([taps.reach(H[i], Ho[i], top[i], wh[i]) for i in range(n)], dtype=np.int64).reshape(-1, 2)
+        r0, r1 = reach[:, 0], reach[:, 1]
+        assert (r0 >= 0).all() and (r1 <= H).all() and (r0 < r1).all()
+    out_sizes = np.stack([wh, ww], axis=1)
+    need_h, need_v = bool(((W != Wo) | (ww != Wo)).any()), bool(((H != Ho) | (wh != Ho)).any())
+    if not need_h:                                       # the vertical pass reads the source images themselves, all their rows
+        r0, r1 = zeros, H
+    mid_sizes = np.stack([r1 - r0, ww], axis=1)
     mid_offsets, mid_bytes = RaggedImageSet.layout(mid_sizes, C)
     if packed_out:
-        nb = Ho * Wo * C
+        nb = wh * ww * C
         out_offsets, out_bytes = np.cumsum(nb) - nb, int(nb.sum())
     else:
         out_offsets, out_bytes = RaggedImageSet.layout(out_sizes, C)
     src_offsets = np.asarray(src_offsets, dtype=np.int64)
 
-    def axis_pass(src_off, dst_off, outer, a_in, a_out, inner):
+    def axis_pass(src_off, dst_off, outer, a_in, a_full, a_out, inner, first):
         ent = {}
-        for pair in set(zip(a_in.tolist(), a_out.tolist())):
+        for pair in set(zip(a_in.tolist(), a_full.tolist())):
             ent[pair] = taps.entry(*pair)
-        e = np.array([ent[p] for p in zip(a_in.tolist(), a_out.tolist())], dtype=np.int64).reshape(-1, 3)
-        desc = np.stack([outer, a_in, a_out, inner, e[:, 0], e[:, 1], e[:, 2], np.zeros(n, dtype=np.int64)], axis=1)
+        e = np.array([ent[p] for p in zip(a_in.tolist(), a_full.tolist())], dtype=np.int64).reshape(-1, 3)
+        desc = np.stack([outer, a_in, a_out, inner, e[:, 0], e[:, 1], e[:, 2], first], axis=1)
         if desc.max() >= 1 << 31:
             raise ValueError("resize_u8: an image of this set is too large for the pass descriptors (2^31)")
         return (np.ascontiguousarray(np.stack([src_off, dst_off], axis=1).astype(np.int64)), np.ascontiguousarray(desc.astype(np.int32)),
                 int((outer * a_out * inner).max()))
 
     ones, cs = np.ones(n, dtype=np.int64), np.full(n, C, dtype=np.int64)
-    plan = dict(out_sizes=out_sizes.astype(np.int32), mid_offsets=mid_offsets, mid_bytes=mid_bytes, out_offsets=out_offsets.astype(np.int64),
-                out_bytes=out_bytes, h=None, v=None)
-    if need_h:                                           # [H, W, C] -> [H, Wo, C]: into the scratch when a vertical pass follows
-        plan["h"] = axis_pass(src_offsets, mid_offsets if need_v else plan["out_offsets"], H, W, Wo, cs)
-    if need_v:                                           # [H, Wo, C] -> [Ho, Wo, C], the row is `inner`
-        plan["v"] = axis_pass(mid_offsets if need_h else src_offsets, plan["out_offsets"], ones, H, Ho, Wo * C)
+    plan = dict(out_sizes=out_sizes.astype(np.int32), mid_sizes=mid_sizes.astype(np.int32), mid_offsets=mid_offsets, mid_bytes=mid_bytes,
+                out_offsets=out_offsets.astype(np.int64), out_bytes=out_bytes, h=None, v=None)
+    if need_h:                                           # rows [r0, r1) of [H, W, C] -> [r1 - r0, ww, C]: into the scratch when a vertical pass follows
+        plan["h"] = axis_pass(src_offsets + r0 * W * C, mid_offsets if need_v else plan["out_offsets"], r1 - r0, W, Wo, ww, cs, left)
+    if need_v:                                           # [H, ww, C] -> [wh, ww, C], the row is `inner`
+        plan["v"] = axis_pass(mid_offsets - r0 * ww * C if need_h else src_offsets, plan["out_offsets"], ones, H, Ho, wh, ww * C, top)
     return plan
 
 
-def _resize_ragged(rs, size, filt):
+def _run_resize_plan(rs, plan, taps, out):
+    """the one or two launches of a plan of `ragged_resize_plan` over the set `rs`, into the flat uint8 `out`"""
     from ._lib import check, lib
-    if not rs.is_cuda:
-        raise RuntimeError("resize_u8 needs the set on a GPU (there is no CPU fallback)")
-    pair = not isinstance(size, int)
-    taps = _TapArena(filt)
-    plan = ragged_resize_plan(rs.sizes, rs.channels, size, taps, rs.offsets_host, pair)
-    n, C, dev = len(rs), rs.channels, rs.device
-    if plan["h"] is None and plan["v"] is None:          # Resize leaves every image as it is
-        return rs.as_tensor() if pair else rs
+    n, dev = len(rs), rs.device
     st = torch.cuda.current_stream().cuda_stream
-    out = torch.zeros(plan["out_bytes"], dtype=torch.uint8, device=dev)        # zeros: the gaps between aligned starts
     taps_dev = taps.tensor().to(dev)
     mid = torch.empty(plan["mid_bytes"], dtype=torch.uint8, device=dev) if plan["h"] and plan["v"] else None     # freed on return
     cur = rs.arena
@@ -453,10 +483,54 @@ def _resize_ragged(rs, size, filt):
         check(lib.eoe_ragged_resize_pass_u8(cur.data_ptr(), dst.data_ptr(), offs_d.data_ptr(), desc_d.data_ptr(), taps_dev.data_ptr(), n,
                                             biggest, st), "eoe_ragged_resize_pass_u8")
         cur = dst
+
+
+def _resize_ragged(rs, size, filt):
+    if not rs.is_cuda:
+        raise RuntimeError("resize_u8 needs the set on a GPU (there is no CPU fallback)")
+    pair = not isinstance(size, int)
+    taps = _TapArena(filt)
+    plan = ragged_resize_plan(rs.sizes, rs.channels, size, taps, rs.offsets_host, pair)
+    n, C, dev = len(rs), rs.channels, rs.device
+    if plan["h"] is None and plan["v"] is None:          # Resize leaves every image as it is
+        return rs.as_tensor() if pair else rs
+    out = torch.zeros(plan["out_bytes"], dtype=torch.uint8, device=dev)        # zeros: the gaps between aligned starts
+    _run_resize_plan(rs, plan, taps, out)
     if pair:
         h, w = plan["out_sizes"][0]
         return out.view(n, int(h), int(w), C)
     return RaggedImageSet.from_parts(out, plan["out_offsets"], plan["out_sizes"], C)
+
+
+def resize_window_u8(rs, size, window, interpolation="bilinear", out=None):
+    """Resize(size) of every image of a `RaggedImageSet`, then the crop `window` = (top, left, height, width) of the resized image --
+    int [n, 4], one height and one width for the whole set -- computing only the window: uint8 [n, height, width, C], byte for
+    byte `resize_u8(rs, size, interpolation)` followed by that crop.  Each pass of `eoe_ragged_resize_pass_u8` writes its window of
+    the output axis, and the horizontal pass runs only over the source rows the vertical window's taps touch
+    (`ragged_resize_plan`).  A window that leaves its resized image is a ValueError before any launch.
+    out: a contiguous uint8 tensor of that shape on the set's device to write into (default: a new one)."""
+    import numpy as np
+    from ._lib import EOE_RESIZE_BILINEAR, EOE_RESIZE_BICUBIC
+    if not isinstance(rs, RaggedImageSet):
+        raise TypeError("resize_window_u8 works on a RaggedImageSet (a tensor set takes resize_u8, then crop_flip_u8)")
+    if interpolation not in ("bilinear", "bicubic"):
+        raise ValueError(f"resize_window_u8: interpolation must be 'bilinear' or 'bicubic', not {interpolation!r}")
+    win = np.asarray(window, dtype=np.int64).reshape(-1, 4)
+    if len(win) != len(rs) or (win[:, 2:] != win[0, 2:]).any():
+        raise ValueError(f"resize_window_u8: one (top, left, height, width) per image with one height and width is needed "
+                         f"({len(win)} rows for {len(rs)} images)")
+    taps = _TapArena(EOE_RESIZE_BILINEAR if interpolation == "bilinear" else EOE_RESIZE_BICUBIC)
+    plan = ragged_resize_plan(rs.sizes, rs.channels, size, taps, rs.offsets_host, True, win)
+    shape = (len(rs), int(win[0, 2]), int(win[0, 3]), rs.channels)
+    if out is not None and not (out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous() and out.device == rs.device):
+        raise ValueError(f"resize_window_u8: out must be a contiguous uint8 {list(shape)} on {rs.device}")
+    if not rs.is_cuda:
+        raise RuntimeError("resize_window_u8 needs the set on a GPU (there is no CPU fallback)")
+    if plan["h"] is None and plan["v"] is None:          # every window is its whole image, which Resize leaves as it is
+        return rs.as_tensor() if out is None else out.copy_(rs.as_tensor())
+    out = torch.empty(shape, dtype=torch.uint8, device=rs.device) if out is None else out
+    _run_resize_plan(rs, plan, taps, out)
+    return out
 
 
 def resize_u8(src_u8, size, interpolation="bilinear"):
@@ -559,7 +633,13 @@ CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.261302
 
 def clip_preprocess(src_u8, n_px=224):
     """CLIP's `_transform` (`clip_official/clip/clip.py:58-65`): Resize(n_px, bicubic) -> CenterCrop(n_px) -> ToTensor ->
-    Normalize(CLIP mean / std), on a uint8 NHWC set in HBM -> fp32 NCHW"""
+    Normalize(CLIP mean / std), on a uint8 NHWC set in HBM -> fp32 NCHW.  A `RaggedImageSet` (RGB) goes through
+    `clip_preprocess_ragged`: each image is resized at its own aspect ratio and only its centre window is computed."""
+    if isinstance(src_u8, RaggedImageSet):
+        u8 = clip_preprocess_ragged(src_u8, n_px)
+        p = torch.zeros((u8.shape[0], 4), dtype=torch.int32)
+        p[:, 0] = torch.arange(u8.shape[0], dtype=torch.int32)
+        return augment_batch(u8, p.to(u8.device), (int(n_px), int(n_px)), CLIP_MEAN, CLIP_STD, True, 0.0, 0)
     r = resize_u8(src_u8, n_px, "bicubic")
     n, H, W, _ = r.shape
     # torchvision's CenterCrop: top = int(round((H - n_px) / 2.0))
@@ -567,6 +647,31 @@ def clip_preprocess(src_u8, n_px=224):
     p = torch.stack([idx, torch.full_like(idx, int(round((H - n_px) / 2.0))), torch.full_like(idx, int(round((W - n_px) / 2.0))),
                      torch.zeros_like(idx)], dim=1).to(torch.int32).to(r.device)
     return augment_batch(r, p, (n_px, n_px), CLIP_MEAN, CLIP_STD, True, 0.0, 0)
+
+
+def clip_window(sizes, n_px):
+    """int64 [n, 4] = (top, left, n_px, n_px): where CLIP's CenterCrop(n_px) lies in each image of `sizes` (int [n, 2]) after its
+    Resize(n_px) -- the `resized_hw` target, the origin torchvision's, int(round((s - n_px) / 2.0)) with Python's half-to-even
+    (`center_origins`).  The shorter side becomes n_px, so the window lies inside the resized image and cuts only the longer axis."""
+    import numpy as np
+    full = np.array([resized_hw(h, w, int(n_px)) for h, w in np.asarray(sizes).reshape(-1, 2)], dtype=np.int64).reshape(-1, 2)
+    return np.concatenate([center_origins(full, n_px), np.full((len(full), 2), int(n_px), dtype=np.int64)], axis=1)
+
+
+def clip_preprocess_ragged(rs, n_px=224, out=None):
+    """the PIL part of CLIP's `_transform` on RAW images of mixed sizes (`clip_official/clip/clip.py:58-65`, what the test split of
+    `main/train_clip_imagenet.py`, `train_clip_cub.py`, `train_clip_dtd.py`, `train_clip_mvtec.py` gets: `val_transform` is empty,
+    `training/clip.py:44-46`): Resize(n_px, BICUBIC) with the aspect ratio kept, then CenterCrop(n_px) -> uint8 [n, n_px, n_px, 3],
+    packed, byte for byte Pillow's `resize` at `resized_hw` followed by the crop at torchvision's origin.  Only the window is
+    computed (`resize_window_u8`): 224 of the 298 columns of a 4 : 3 image.  The filter is CLIP's bicubic.  RGB only."""
+    if not isinstance(rs, RaggedImageSet):
+        raise TypeError("clip_preprocess_ragged works on a RaggedImageSet (a tensor set takes clip_preprocess)")
+    if rs.channels != 3:
+        raise ValueError(f"clip_preprocess_ragged: the ragged CLIP path is RGB only, not {rs.channels} channel(s): convert the images "
+                         "to RGB before packing them")
+    if int(n_px) < 1:
+        raise ValueError(f"clip_preprocess_ragged: n_px must be positive, not {n_px}")
+    return resize_window_u8(rs, int(n_px), clip_window(rs.sizes, n_px), "bicubic", out)
 
 
 _TAP_TABLES = {}             # (crop, n_px, filter, device) -> (bounds, kk) on that device: uploaded once, not per step
@@ -636,6 +741,38 @@ def gray_set(images_u8, device):
 def _resident(t, device):
     """an image set as the source keeps it: on the device; a tensor contiguous, a RaggedImageSet as packed"""
     return t.to(device) if isinstance(t, RaggedImageSet) else t.to(device).contiguous()
+
+
+def _set_channels(t):
+    """the channel count of a resident image set, a tensor [n, H, W, C] or a RaggedImageSet"""
+    return t.channels if isinstance(t, RaggedImageSet) else int(t.shape[3])
+
+
+def _check_clip_ragged_half(what, rs, crop, n_px):
+    """`clip_preprocessing` on a train half that stays ragged (`main/train_clip_cub.py:26`, `train_clip_dtd.py:26`: Resize(256) keeps
+    the aspect ratio): after RandomCrop(n_px) CLIP's PIL stage is the identity on RGB, so the ragged chain runs as it is, with CLIP's
+    Normalize.  Any other crop would need the per-sample upsample of a ragged crop, which no runner has"""
+    if int(crop) != n_px:
+        raise NotImplementedError(f"clip_preprocessing on a RaggedImageSet needs crop == n_px (the {what} set is ragged, crop {crop}, "
+                                  f"n_px {n_px}): resampling a ragged crop per sample is not built, and no runner of the reference "
+                                  "needs it (a pair `resize=` gives the tensor path)")
+    if rs.channels != 3:
+        raise ValueError(f"clip_preprocessing on a RaggedImageSet is RGB only; the {what} set has {rs.channels} channel(s): convert "
+                         "the images to RGB before packing them")
+
+
+def _check_clip_ragged_test(rs, test_resize, device):
+    """`clip_preprocessing` with a ragged test set: CLIP's own transform runs alone on the RAW test images, once, at construction
+    (`clip_preprocess_ragged`), which is a HIP kernel"""
+    if test_resize is not None:
+        raise ValueError("test_resize= cannot be combined with clip_preprocessing on a ragged test set: CLIP's transform is applied to "
+                         "the raw test images (val_transform is empty, training/clip.py:44-46)")
+    if rs.channels != 3:
+        raise ValueError(f"clip_preprocessing on a RaggedImageSet is RGB only; the test set has {rs.channels} channel(s): convert the "
+                         "images to RGB before packing them")
+    if torch.device(device).type != "cuda":
+        raise NotImplementedError("clip_preprocessing on a RaggedImageSet test set is applied at construction by a HIP kernel (the "
+                                  f"windowed ragged Resize): not built for device {str(device)!r}")
 
 
 def _check_crop_fits(what, rs, crop, padding):
@@ -727,7 +864,16 @@ class ResidentImageSource:
         (`datasets/imagenet.py:89-93, 273-278`), with the unchanged `fit_statistics`.  (The tensor path fits over the whole resized
         images, which is the same thing only where the crop is the image.)
       * `normal_index`, `set_oe_subset`, MSMs and `defer_normalize` work as on tensors: they select rows or act on the batch.
-    `clip_preprocessing` and `grayscale=True` are refused with a ragged set."""
+      * `clip_preprocessing=n_px` with ragged sets is the chain of the 224 x 224 CLIP runners (`main/train_clip_imagenet.py`,
+        `train_clip_cub.py`, `train_clip_dtd.py`, `train_clip_mvtec.py`), each set on its own.  A ragged TEST set gets CLIP's
+        transform alone on the raw images -- Resize(n_px, BICUBIC) at each image's aspect ratio, CenterCrop(n_px) -- once, at
+        construction (`clip_preprocess_ragged`: only the centre window is computed), and becomes a `[n, n_px, n_px, 3]` tensor whose
+        batches take the identity path; `test_resize=` is a ValueError with it, since CLIP's transform works on the raw images.  A
+        ragged NORMAL / OE set (after `resize=int`; a pair `resize=` gives the tensor and the tensor path) needs `crop == n_px`:
+        after RandomCrop(n_px) CLIP's PIL stage is the identity on RGB, so the ragged chain above runs unchanged -- same draws, draw
+        order and kernels as without the option -- with CLIP's mean / std (or the given three values).  Another crop is a
+        NotImplementedError (no runner resamples a ragged crop), a 1-channel ragged set a ValueError: the ragged CLIP path is RGB.
+    `grayscale=True` is refused with a ragged set."""
 
     nominal_label, anomalous_label = 0, 1
 
@@ -738,13 +884,9 @@ class ResidentImageSource:
         color_jitter: (brightness, contrast, saturation, hue) of `transforms.ColorJitter`, drawn per sample per step;
         clip_preprocessing: n_px of CLIP's transform inside the chain (the class docstring)"""
         dev = torch.device(device)
-        if any(isinstance(t, RaggedImageSet) for t in (normal_u8, oe_u8, test_u8)):
-            if clip_preprocessing is not None:
-                raise NotImplementedError("clip_preprocessing on a RaggedImageSet is not built: its upsample kernel takes square crops "
-                                          "of one small set; Resize the set to one (h, w) first (resize_u8 with a pair gives the tensor)")
-            if grayscale:
-                raise NotImplementedError("grayscale=True on a RaggedImageSet is not built: convert the images to one channel before "
-                                          "packing them (a 1-channel RaggedImageSet is accepted)")
+        if grayscale and any(isinstance(t, RaggedImageSet) for t in (normal_u8, oe_u8, test_u8)):
+            raise NotImplementedError("grayscale=True on a RaggedImageSet is not built: convert the images to one channel before "
+                                      "packing them (a 1-channel RaggedImageSet is accepted)")
         if clip_preprocessing is not None:
             if normalize is not None or ds_statistics is not None:
                 raise ValueError("clip_preprocessing normalises with CLIP's own (or the given three-valued) mean / std, as "
@@ -759,6 +901,13 @@ class ResidentImageSource:
                                           "(n_px >= crop) is built")
             if mean is None and std is None:
                 mean, std = CLIP_MEAN, CLIP_STD
+            # a ragged half stays ragged unless `resize` is a pair (which gives the tensor): CLIP's PIL stage is then the identity
+            # only on an RGB crop of n_px, and Normalize with CLIP's statistics is all that is new
+            for what, t in (("normal", normal_u8), ("OE", oe_u8)):
+                if isinstance(t, RaggedImageSet) and (resize is None or isinstance(resize, int)):
+                    _check_clip_ragged_half(what, t, crop, int(clip_preprocessing))
+            if isinstance(test_u8, RaggedImageSet):
+                _check_clip_ragged_test(test_u8, test_resize, dev)
         if grayscale and color_jitter is not None:
             raise ValueError("color_jitter works on RGB images and cannot be combined with grayscale=True (no chain of the "
                              "reference has both)")
@@ -771,6 +920,10 @@ class ResidentImageSource:
             self.normal, self.oe = resize_u8(self.normal, resize, interpolation), resize_u8(self.oe, resize, interpolation)
         if test_resize is not None:
             self.test = resize_u8(self.test, test_resize, interpolation)
+        if clip_preprocessing is not None and isinstance(self.test, RaggedImageSet):
+            # CLIP's transform alone on the raw test images (val_transform is empty, training/clip.py:44-46): deterministic, so it runs
+            # once, here; the test batches then take the identity path (a 3-channel set whose size is n_px already)
+            self.test = clip_preprocess_ragged(self.test, int(clip_preprocessing))
         self.color_jitter = color_jitter
         self.test_y = test_labels.clone()
         self.crop, self.padding, self.mean, self.std = int(crop), int(padding), mean, std
@@ -786,7 +939,7 @@ class ResidentImageSource:
             if th != tw:
                 raise ValueError(f"clip_preprocessing needs square test images, not {th} x {tw}: Resize(n_px) of another shape is "
                                  "not n_px x n_px and CenterCrop would cut it")
-            for what, side, chans in (("crop", self.crop, self.normal.shape[3]), ("test images", th, self.test.shape[3])):
+            for what, side, chans in (("crop", self.crop, _set_channels(self.normal)), ("test images", th, self.test.shape[3])):
                 if self._clip_px(side, chans) is not None and not (side <= px and side <= 64 and px <= 256):
                     raise NotImplementedError(f"clip_preprocessing={px} on {what} of {side} px: only upsampling from at most 64 px to "
                                               "at most 256 px is built")
@@ -860,7 +1013,7 @@ class ResidentImageSource:
         claimed MSMs, which the trainer then leaves out of the step batch's apply_msms; test batches (centre crops, no noise)
         stay with apply_msms."""
         self._pre_msms = [m for m in msms if m.transform_str == "sharpen" and m.ds_part_str in ("train_nominal", "train_oe")]
-        if self._pre_msms and self.clip_preprocessing is not None and self._clip_px(self.crop, self.normal.shape[3]) is not None:
+        if self._pre_msms and self.clip_preprocessing is not None and self._clip_px(self.crop, _set_channels(self.normal)) is not None:
             self._pre_msms = []
             raise NotImplementedError("a train sharpen MSM works on the uint8 crop in front of clip_preprocessing's upsample; that "
                                       "combination is not built")
@@ -877,7 +1030,7 @@ class ResidentImageSource:
         jitter: (factors, order) of a ragged half under color_jitter -- ColorJitter and the crop / flip are then one uint8 stage
         (`color_jitter_crop_u8`) in front of the sharpen MSMs and of augment_batch with identity params"""
         ops = [m for m in getattr(self, "_pre_msms", ()) if (m.ds_part_str == "train_nominal") == nominal]
-        if self.clip_preprocessing is not None and self._clip_px(self.crop, src.shape[3]) is not None:   # a sharpen MSM is refused together with it (pre_tensor_msms)
+        if self.clip_preprocessing is not None and self._clip_px(self.crop, _set_channels(src)) is not None:   # a sharpen MSM is refused together with it (pre_tensor_msms)
             return augment_resize_batch(src, p, self.crop, self.clip_preprocessing, mean, std, self.flip_first, self.noise_std, seed)
         if (not ops and jitter is None) or p.shape[0] == 0:
             return augment_batch(src, p, (self.crop, self.crop), mean, std, self.flip_first, self.noise_std, seed)
@@ -1000,16 +1153,19 @@ class ResidentImageSource:
         return (torch.arange(s, min(s + batch_size, len(self.test_y))) for s in range(0, len(self.test_y), batch_size))
 
     def _test_batch(self, idx):
-        """(images, labels, indices) of the listed test rows (no clip_preprocessing): CenterCrop(crop) of each image -- a ragged set:
+        """(images, labels, indices) of the listed test rows (without clip_preprocessing, or where its stage is the identity): CenterCrop(crop) of each image -- a ragged set:
         at its own origin (train_imagenet.py:38-41, `center_origins`)"""
+        # under clip_preprocessing a test set that comes here is n_px x n_px x 3 -- given so, or made so from a ragged set at
+        # construction: CLIP's transform alone is the identity on it, whatever the train crop is (val_transform is empty)
+        side = self.crop if self.clip_preprocessing is None else self.clip_preprocessing
         if isinstance(self.test, RaggedImageSet):
-            tl = torch.from_numpy(center_origins(self.test.sizes, self.crop))
+            tl = torch.from_numpy(center_origins(self.test.sizes, side))
             p = torch.stack([idx, tl[idx, 0], tl[idx, 1], torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
         else:
             Hs, Ws = self.test.shape[1], self.test.shape[2]
-            p = torch.stack([idx, torch.full_like(idx, (Hs - self.crop) // 2), torch.full_like(idx, (Ws - self.crop) // 2),
+            p = torch.stack([idx, torch.full_like(idx, (Hs - side) // 2), torch.full_like(idx, (Ws - side) // 2),
                              torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
-        return augment_batch(self.test, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx
+        return augment_batch(self.test, p, (side, side), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx
 
     PREVIEW_SEED = 0x9E3779B1
 
@@ -1096,8 +1252,16 @@ class LabelledImageSet:
             self.train, self.test, self.oe = (gray_set(t, dev) for t in (train_u8, test_u8, oe_u8))
             source_kw = dict(source_kw, grayscale=True)
         else:
+            px, rsz = source_kw.get("clip_preprocessing"), source_kw.get("resize")
+            for what, t in (("normal", train_u8), ("OE", oe_u8)):             # the source's refusal, in front of the device work below
+                if px is not None and isinstance(t, RaggedImageSet) and (rsz is None or isinstance(rsz, int)) and isinstance(crop, int):
+                    _check_clip_ragged_half(what, t, crop, int(px))
+            if px is not None and isinstance(test_u8, RaggedImageSet):
+                # CLIP's transform on the raw test images is the same for every task: once, here, not once per class and seed
+                _check_clip_ragged_test(test_u8, source_kw.get("test_resize"), dev)
+                test_u8 = clip_preprocess_ragged(_resident(test_u8, dev), int(px))
             self.train, self.test, self.oe = (_resident(t, dev) for t in (train_u8, test_u8, oe_u8))
-        self.train_classes = torch.as_tensor(train_classes, dtype=torch.int64).clone()
+        self.train_classes =torch.as_tensor(train_classes, dtype=torch.int64).clone()
         self.test_classes = torch.as_tensor(test_classes, dtype=torch.int64).clone()
         self.classes = list(classes)
         self.crop, self.source_kw, self.device = crop, dict(source_kw), dev

@@ -934,11 +934,22 @@ int eoe_augment_resize_batch(const uint8_t* src, int64_t n_src, int Hs, int Ws, 
  *                                    second applies the ops under the crop window only; the padding stays 0
  *   eoe_ragged_resize_pass_u8        eoe_resize_pass_u8 for every image of a set in one launch: image i is src + offs[2 i] as
  *                                    [outer, axis_in, inner] -> dst + offs[2 i + 1] as [outer, axis_out, inner] (offs int64 [n, 2]),
- *                                    desc int32 [n, 8] = (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, 0) where
+ *                                    desc int32 [n, 8] = (outer, axis_in, axis_out, inner, bounds_at, kk_at, ksize, first) where
  *                                    bounds_at / kk_at are positions in `taps`, an int32 array holding the eoe_resize_coeffs
- *                                    tables (ksize_cap = ksize) of every distinct (in, out) of the set; an image with axis_in ==
- *                                    axis_out is copied (Pillow skips that pass).  max_out_bytes: the largest image's output,
- *                                    which sizes the launch.  All arrays on the device; the taps are computed on the host. */
+ *                                    tables (ksize_cap = ksize) of every distinct (in, out) of the set; an image whose axis is at
+ *                                    its target already has ksize = 0 and is copied (Pillow skips that pass).  max_out_bytes: the
+ *                                    largest image's output, which sizes the launch.  All arrays on the device; the taps are
+ *                                    computed on the host.
+ *                                    first: a window on the output axis (CenterCrop behind Resize, clip_official/clip/clip.py:
+ *                                    58-65).  The pass writes outputs [first, first + axis_out) of the FULL output axis, packed as
+ *                                    [outer, axis_out, inner]; bounds_at / kk_at name the tables of the full axis, whose row
+ *                                    first + x is output x; a ksize = 0 pass copies positions [first, first + axis_out) of
+ *                                    axis_in.  first = 0 with axis_out the full axis is the whole pass, bit for bit what it was
+ *                                    before the field had a meaning.  offs[2 i] is signed: behind a horizontal pass that wrote only
+ *                                    source rows [r0, r1) the vertical pass (outer = 1) is given the start of the intermediate minus
+ *                                    r0 rows, and its taps, all within [r0, r1), land inside it.  The descriptors live on the
+ *                                    device, so the window is checked where it is made, on the host (data.ragged_resize_plan:
+ *                                    first < 0 or first + count beyond the full axis is a ValueError before any launch). */
 int eoe_ragged_augment_batch(const uint8_t* arena, const int64_t* offsets, const int32_t* sizes, int64_t n_src, int C,
                              const int32_t* params, const float* mean, const float* std, float* out, int n, int Ho, int Wo,
                              int flip_first, float noise_std, uint64_t seed, void* stream);
