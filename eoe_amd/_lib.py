@@ -165,6 +165,8 @@ SIGNATURES = {
     "eoe_cast": [_vp, _vp, _sz, C.c_int, _vp],
     "eoe_attn_fwd": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_attn_bwd": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_attn_long_fwd": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "eoe_attn_long_bwd": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_attn_causal_fwd": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_clip_token_embed": [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_clip_eot_ln": [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, C.c_int, _vp],

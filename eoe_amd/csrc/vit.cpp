@@ -72,9 +72,9 @@ eoe_gemm_args gemm(const eoe_vit_block_fwd_args* a, const void* A, const void* B
 
 int check_fwd(const eoe_vit_block_fwd_args* a) {
     if (!a) return eoe_set_error(EOE_ERR_ARG, "vit_block: null args");
-    if (a->n <= 0 || a->L <= 0 || a->L > 64 || a->heads <= 0 || a->D != a->heads * 64)
-        return eoe_set_error(EOE_ERR_ARG, "vit_block: unsupported shape n=%d L=%d D=%d heads=%d (need D = 64*heads, L <= 64)",
-                             a->n, a->L, a->D, a->heads);
+    if (a->n <= 0 || a->L <= 0 || a->L > EOE_ATTN_LONG_MAX_L || a->heads <= 0 || a->D != a->heads * 64)
+        return eoe_set_error(EOE_ERR_ARG, "vit_block: unsupported shape n=%d L=%d D=%d heads=%d (need D = 64*heads, L <= %d)",
+                             a->n, a->L, a->D, a->heads, EOE_ATTN_LONG_MAX_L);
     if (!a->ln1_g || !a->ln1_b || !a->ln2_g || !a->ln2_b || !a->b_in || !a->b_out || !a->b_fc || !a->b_proj || !a->w_in ||
         !a->w_out || !a->w_fc || !a->w_proj || !a->x_in || !a->x_mid || !a->x_out || !a->xn1 || !a->qkv || !a->att ||
         !a->xn2 || !a->hact || !a->stats1 || !a->stats2)      // hpre is optional: forward-only callers pass NULL
@@ -91,7 +91,9 @@ extern "C" int eoe_vit_block_fwd(const eoe_vit_block_fwd_args* a, void* stream) 
     TRY(eoe_layernorm_fwd(a->x_in, D, a->ln1_g, a->ln1_b, a->xn1, a->stats1, M, D, a->eps, dt, 0, stream));
     eoe_gemm_args g = gemm(a, a->xn1, a->w_in, a->qkv, a->b_in, M, 3 * D, D, D, D, 3 * D, dt);
     TRY(eoe_gemm_nt(&g, stream));
-    TRY(eoe_attn_fwd(a->qkv, a->att, a->n, a->L, a->heads, dt, stream));
+    // one (image, head) per wavefront up to 64 tokens, 64 x 64 blocks with an online softmax above (attention_long.hip)
+    TRY(a->L <= 64 ? eoe_attn_fwd(a->qkv, a->att, a->n, a->L, a->heads, dt, stream)
+                   : eoe_attn_long_fwd(a->qkv, a->att, a->n, a->L, a->heads, dt, stream));
     // (cls_only: from here on only the class-token rows -- row i*L of image i, gathered by the row strides of the GEMM's A operand
     //  and of its residual input; everything downstream is a dense [n, ...] matrix)
     const int Mo = a->cls_only ? a->n : M, ldrow = a->cls_only ? a->L * D : D;
@@ -191,7 +193,8 @@ extern "C" int eoe_vit_block_bwd(const eoe_vit_block_bwd_args* b, void* stream) 
     g = gemm(a, b->d16_c, a->w_out_t, b->d16_b, nullptr, Mo, D, D, D, D, ldrow, dt);           // d att
     TRY(eoe_gemm_nt(&g, stream));
     // + db_in = column sums of dqkv, from the attention kernel's accumulators when the scratch is there
-    TRY(eoe_attn_bwd(a->qkv, b->d16_b, b->dqkv, red_attn ? b->g_b_in : nullptr, red_attn, a->n, a->L, a->heads, dt, stream));
+    TRY(a->L <= 64 ? eoe_attn_bwd(a->qkv, b->d16_b, b->dqkv, red_attn ? b->g_b_in : nullptr, red_attn, a->n, a->L, a->heads, dt, stream)
+                   : eoe_attn_long_bwd(a->qkv, b->d16_b, b->dqkv, red_attn ? b->g_b_in : nullptr, red_attn, a->n, a->L, a->heads, dt, stream));
     g = gemm(a, b->dqkv, a->w_in_t, b->d16_b, nullptr, M, D, 3 * D, 3 * D, 3 * D, D, dt);      // d xn1
     TRY(eoe_gemm_nt(&g, stream));
     if (!b->red_scratch) TRY(eoe_colsum(b->dqkv, 3 * D, b->g_b_in, M, 3 * D, dt, 1, stream));

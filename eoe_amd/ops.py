@@ -224,6 +224,27 @@ def attn_bwd(qkv, dout, dqkv, n, L, heads, dbias=None):
     return dqkv
 
 
+ATTN_SHORT_MAX_L = 64             # eoe_attn_fwd / eoe_attn_bwd: one (image, head) per wavefront
+ATTN_LONG_MAX_L = 640             # EOE_ATTN_LONG_MAX_L (include/eoe_hip.h)
+
+
+def attn_long_fwd(qkv, out, n, L, heads):
+    """attn_fwd for ATTN_SHORT_MAX_L < L <= ATTN_LONG_MAX_L (csrc/attention_long.hip): same layout; nothing is saved for the backward"""
+    _chk(qkv, out)
+    check(lib.eoe_attn_long_fwd(_p(qkv), _p(out), n, L, heads, dtype_code(qkv.dtype), _stream()), "eoe_attn_long_fwd")
+    return out
+
+
+def attn_long_bwd(qkv, dout, dqkv, n, L, heads, dbias=None):
+    """attn_bwd for ATTN_SHORT_MAX_L < L <= ATTN_LONG_MAX_L: dqkv from (qkv, dout), the row statistics recomputed; dbias (optional fp32
+    [3D]) += column sums of dqkv (exact zeros on the K third)"""
+    _chk(qkv, dout, dqkv, dbias)
+    part = scratch("attn_bias_part", (n * 3 * heads * 64,), torch.float32, qkv.device) if dbias is not None else None
+    check(lib.eoe_attn_long_bwd(_p(qkv), _p(dout), _p(dqkv), _p(dbias), _p(part), n, L, heads, dtype_code(qkv.dtype), _stream()),
+          "eoe_attn_long_bwd")
+    return dqkv
+
+
 def attn_causal_fwd(qkv, out, n, L, heads):
     """causal attention of CLIP's text tower (key j reaches query i only for j <= i), same layout as attn_fwd; 1 <= L <= 128"""
     _chk(qkv, out)

@@ -216,6 +216,15 @@ int eoe_attn_fwd(const void* qkv, void* out, int n, int L, int heads, int dtype,
  * through bias_scratch (fp32 [n, 3D], required with dbias) and a fixed-order reduce kernel -- no separate pass over dqkv */
 int eoe_attn_bwd(const void* qkv, const void* dout, void* dqkv, float* dbias, float* bias_scratch, int n, int L, int heads,
                  int dtype, void* stream);
+/* the same two operations for long sequences, 64 < L <= EOE_ATTN_LONG_MAX_L (ViT-B/16 at 224^2: 197 tokens, at 384^2: 577): blocks of
+ * 64 queries x 64 keys with an online softmax, csrc/attention_long.hip.  Same layouts, same dbias / bias_scratch contract (the K third
+ * of dbias receives exact zeros).  The forward saves nothing for the backward, which recomputes the row statistics; neither allocates;
+ * two runs give the same bits.  A length outside the range, n or heads <= 0 or a dtype other than EOE_F16 / EOE_BF16 is refused before
+ * any launch (eoe_attn_fwd / eoe_attn_bwd keep refusing L > 64: the caller chooses). */
+#define EOE_ATTN_LONG_MAX_L 640
+int eoe_attn_long_fwd(const void* qkv, void* out, int n, int L, int heads, int dtype, void* stream);
+int eoe_attn_long_bwd(const void* qkv, const void* dout, void* dqkv, float* dbias, float* bias_scratch, int n, int L, int heads,
+                      int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * CLIP's text tower (clip/model.py:343-356 CLIP.encode_text), forward only (the prompts are encoded once per run, under no_grad,
@@ -352,6 +361,8 @@ int eoe_grads_nonfinite(const float* g, const eoe_adam_chunk* chunks /*device*/,
 /* ------------------------------------------------------------------------------------------------------
  * fused ViT residual block (clip/model.py:167-188 ResidualAttentionBlock.forward and its backward):
  * one call launches the whole kernel chain of a block on `stream` (no host round trips in between).
+ * The attention of the block is eoe_attn_fwd / eoe_attn_bwd for L <= 64 and eoe_attn_long_fwd / eoe_attn_long_bwd above, up to
+ * EOE_ATTN_LONG_MAX_L; no argument changes with the length.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t n, L, D, heads, dtype;   /* rows M = n*L; hidden = 4*D */
