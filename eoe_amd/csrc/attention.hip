@@ -9,29 +9,12 @@
 //     blocks its ds_read_b64_tr_b16 transposed reads fetch.
 // Backward recomputes the probabilities (L*L is tiny) in both orientations: lane = query for dQ, and
 // lane = key (operands swapped) for dV and dK, so that every product sums over an accumulator-row index.
-#include "common.h"
+#include "attn_frag.h"
 
 int g_attn_flags = 0;            // eoe_set_option("attn_flags", bit 0: the one-wave backward kernel)
 
 namespace {
-
-constexpr int ROWB = 160;            // LDS row pitch in bytes (64 x 16-bit + pad): conflict-free transposed reads
-constexpr int TILEB = 64 * ROWB;     // one 64 x 64 operand image
-// (round 5) The 16-byte chunks of ODD rows are stored pairwise swapped (in-row byte offset ^ 16).  With the hardware's lane groups (a
-// ds_read_b64_tr_b16 is served in two groups of 32 lanes, banks (a / 4) mod 64) the interleaved transposing read tfrag_il -- dword 40 row + 8 p +
-// 2 tc over rows 0-7 x p 0-3 -- put 32 lanes on 16 banks FOUR ways (8 LDS cycles for an ideal 2; attn_bwd4: SQ_LDS_BANK_CONFLICT 3.56 M cycles
-// per launch); with the swap two ways, the floor for 8-byte pieces of 16-byte-aligned rows (searched by simulation over every GF(2)-linear
-// 3-bit function of the row, pitches 128 / 160 / 192); the ds_read_b128 fragment reads and the plain transposing reads stay conflict-free.
-// attn_bwd 0.480 -> 0.465 ms per step, step 10.256 -> 10.222 (three interleaved pairs, tools/cflags_ab.sh -DEOE_ATTN_NO_RSWZ).  Also measured: an
-// unpadded 128-byte pitch with the 3-bit term ((row >> 1 & 1) * 3 | row & 4) -- the same conflict profile, 28 KB of LDS per attn_bwd4 workgroup --
-// and five workgroups per CU (amdgpu_waves_per_eu(5, 5): 96 registers, 4 spilled): attn_bwd 0.465 -> 0.509 ms per step; not kept.
-#ifdef EOE_ATTN_NO_RSWZ          // A/B builds (tools/cflags_ab.sh): the round-4 image
-__device__ __forceinline__ int rswz(int) { return 0; }
-#else
-__device__ __forceinline__ int rswz(int row) { return (row & 1) << 4; }
-#endif
-
-template <typename T> using V8 = typename T16<T>::v8;
+using namespace attn_frag;
 
 template <typename T>
 __device__ __forceinline__ V8<T> zero8() {
@@ -58,70 +41,6 @@ __device__ __forceinline__ V8<T> gfrag(const T* src, int ld, int L, int t, int k
     if (row >= L) return zero8<T>();
     return __builtin_bit_cast(V8<T>, *(const u32x4*)(src + (size_t)row * ld + (ks * 4 + (lane >> 4)) * 8));
 }
-// The loads above sit behind `row < L` branches, and hipcc turns every one of them into load -> s_waitcnt vmcnt(0) -> use: a wave's
-// operand fetch became a chain of 8-11 dependent HBM round trips (round 4: attn_fwd's ISA showed eight load/wait/ds_write groups for V alone).
-// The forms below read through a buffer resource that covers the (image, head) slab; a row >= L gets an out-of-range offset, which reads
-// zeros, so the loads are unconditional and a whole batch is in flight before the first wait.
-__device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, int row, int L, unsigned pitchb, unsigned cb) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(row < L ? (unsigned)row * pitchb + cb : EOE_OOB), 0, 0));
-}
-// gfrag through the resource: cb0 = byte offset of the operand's head slice inside a row
-template <typename T>
-__device__ __forceinline__ V8<T> bfrag(__amdgpu_buffer_rsrc_t r, unsigned pitchb, unsigned cb0, int L, int t, int ks, int lane) {
-    return __builtin_bit_cast(V8<T>, bload16(r, t * 16 + (lane & 15), L, pitchb, cb0 + (unsigned)(ks * 4 + (lane >> 4)) * 16u));
-}
-// the same fragment from an LDS image
-template <typename T>
-__device__ __forceinline__ V8<T> lfrag(const char* lds, int t, int ks, int lane) {
-    const int row = t * 16 + (lane & 15);
-    return __builtin_bit_cast(V8<T>, *(const u32x4*)(lds + row * ROWB + (((ks * 4 + (lane >> 4)) * 16) ^ rswz(row))));
-}
-// transposed fragment: lane <-> column 16*tc + (lane&15); element j <-> row perm(s, lane>>4, j) (see header)
-template <typename T>
-__device__ __forceinline__ V8<T> tfrag(const char* lds, int tc, int s, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const char* a = lds + (32 * s + 4 * g + q) * ROWB + (((16 * tc + 4 * p) * 2) ^ rswz(4 * g + q));
-    i16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a));
-    i16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a + 16 * ROWB));
-    i16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return __builtin_bit_cast(V8<T>, r);
-}
-// the same with the COLUMNS of the four tiles tc = 0..3 interleaved: lane <-> column 16*((lane&15)>>2) + 4*tc + (lane&3).  As the A operand of a
-// transposed product (rows of the result = these columns) it leaves lane (lane&15, g = lane>>4) of result tile tc with rows
-// 16*g + 4*tc + 0..3 -- over the four tiles 16 CONSECUTIVE rows per lane: a lane's share of an output row is one 32-byte run
-// (attn_bwd4_kernel's dQ / dK / dV stores) instead of four 8-byte pieces 32 bytes apart.  Only the address each lane hands the transposing read
-// changes.
-template <typename T>
-__device__ __forceinline__ V8<T> tfrag_il(const char* lds, int tc, int s, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const char* a = lds + (32 * s + 4 * g + q) * ROWB + (((16 * p + 4 * tc) * 2) ^ rswz(4 * g + q));
-    i16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a));
-    i16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a + 16 * ROWB));
-    i16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return __builtin_bit_cast(V8<T>, r);
-}
-// two accumulator tiles (rows 32s+0..15 and 32s+16..31 of a transposed product) as the next B operand
-template <typename T>
-__device__ __forceinline__ V8<T> acc_as_operand(const f32x4& lo, const f32x4& hi) {
-    V8<T> r;
-    r[0] = (T)lo[0]; r[1] = (T)lo[1]; r[2] = (T)lo[2]; r[3] = (T)lo[3];
-    r[4] = (T)hi[0]; r[5] = (T)hi[1]; r[6] = (T)hi[2]; r[7] = (T)hi[3];
-    return r;
-}
-
-__device__ __forceinline__ float group_max(float v) {   // over the 4 lanes sharing lane&15
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float group_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-
 // transposed scores -> normalised probabilities in place; returns per-tq (max, sum) through mx/sm
 template <typename T>
 __device__ __forceinline__ void softmax_T(f32x4 (&s)[4][4], int L, float scale, int lane, float (&mx)[4],
@@ -233,37 +152,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 #pragma unroll
     for (int tq = 0; tq < 4; ++tq) {
         const int query = 16 * tq + lr;
-        if (query < L) {
-            T* d = out + ((size_t)img * L + query) * D + h * 64 + 16 * lg;
-            *(u32x4*)d = (u32x4){pk[tq][0][0], pk[tq][0][1], pk[tq][1][0], pk[tq][1][1]};
-            *(u32x4*)(d + 8) = (u32x4){pk[tq][2][0], pk[tq][2][1], pk[tq][3][0], pk[tq][3][1]};
-        }
+        if (query < L) store_row16(out + ((size_t)img * L + query) * D + h * 64 + 16 * lg, pk[tq]);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ backward
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
 // sum over the L tokens of a [token = 16 t + lr][4 columns] accumulator set: in-lane over t, then over the 16 lanes sharing lane>>4
 __device__ __forceinline__ f32x4 token_sum(const f32x4 (&o)[4], int L, int lr) {
     f32x4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (16 * i + lr < L) t += o[i];
-    // the 16 lanes are one DPP row: quad xor 1, quad xor 2, half-row mirror (quads 0<->1, 2<->3 hold equal sums by then), row
-    // mirror -- four VALU instructions per value instead of four ds_bpermute round trips
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float v = t[r];
-        v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
-        v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
-        v += dpp_mov<0x141>(v);     // row_half_mirror
-        v += dpp_mov<0x140>(v);     // row_mirror
-        t[r] = v;
-    }
-    return t;
+    return row16_sum(t);
 }
 // (round 2, measured and rejected: TWO waves per (image, head) -- wave 0 = phase A / dQ, wave 1 = phase B / dK, dV, sharing the three
 //  LDS images, the row statistics handed over behind one workgroup barrier; bitwise identical results, but 256 VGPRs + 88 B of
@@ -475,21 +375,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // so 4 workgroups = 16 waves fit a CU and one workgroup's load / store latency is another's issue time.  Same arithmetic per element
 // as the one-wave kernel (same products, same k order); only the bias column sums associate differently (per-wave partials summed in
 // wave order).
-// column sums over the 16 tokens of one accumulator tile (token = lane & 15): the DPP row reduction of token_sum
-__device__ __forceinline__ f32x4 slab_sum(const f32x4& o, bool valid) {
-    f32x4 t = valid ? o : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float v = t[r];
-        v += dpp_mov<0xB1>(v);
-        v += dpp_mov<0x4E>(v);
-        v += dpp_mov<0x141>(v);
-        v += dpp_mov<0x140>(v);
-        t[r] = v;
-    }
-    return t;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd4_kernel(const T* __restrict__ qkv, const T* __restrict__ dout, T* __restrict__ dqkv,
                                                         float* __restrict__ bias_part, int L, int heads, float scale) {
@@ -647,11 +532,7 @@ __global__ __launch_bounds__(256) void attn_bwd4_kernel(const T* __restrict__ qk
         // phase B's V fragments have long landed; without this use the wait for them sits BEHIND the stores below, and vmcnt cannot tell a
         // load from a store that was issued later: phase B would start with s_waitcnt vmcnt(0), i.e. after the dQ stores have drained
         asm volatile("" : "+v"(vfw[0]), "+v"(vfw[1]));
-        if (mine < L) {
-            T* d = dqp + (size_t)mine * ld + 16 * lg;
-            *(u32x4*)d = (u32x4){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
-            *(u32x4*)(d + 8) = (u32x4){pk[2][0], pk[2][1], pk[3][0], pk[3][1]};
-        }
+        if (mine < L) store_row16(dqp + (size_t)mine * ld + 16 * lg, pk);
     }
     __syncthreads();
 
@@ -700,10 +581,8 @@ __global__ __launch_bounds__(256) void attn_bwd4_kernel(const T* __restrict__ qk
         if (mine < L) {
             T* dv = dqp + (size_t)mine * ld + 2 * D + 16 * lg;
             T* dk = dqp + (size_t)mine * ld + D + 16 * lg;
-            *(u32x4*)dv = (u32x4){pv[0][0], pv[0][1], pv[1][0], pv[1][1]};
-            *(u32x4*)(dv + 8) = (u32x4){pv[2][0], pv[2][1], pv[3][0], pv[3][1]};
-            *(u32x4*)dk = (u32x4){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
-            *(u32x4*)(dk + 8) = (u32x4){pk[2][0], pk[2][1], pk[3][0], pk[3][1]};
+            store_row16(dv, pv);
+            store_row16(dk, pk);
         }
     }
     if (bpart) {

@@ -1,9 +1,9 @@
 // Multi-head self-attention for LONG sequences (64 < L <= EOE_ATTN_LONG_MAX_L tokens, head dim 64; ViT-B/16 at 224^2: L = 197, ViT-B/32
 // at 384^2: L = 145, ViT-B/16 at 384^2: L = 577), no mask, forward and backward.  attention.hip holds one whole (image, head) in one
 // wavefront's registers and stops at 64 tokens; here the sequence is cut into blocks of 64 queries x 64 keys and registers and LDS do not
-// depend on L.  The products, the operand layouts and the transposing LDS reads are attention.hip's (v_mfma_f32_16x16x32_{f16,bf16},
-// scores computed TRANSPOSED so that the probabilities are already the B operand of the next product, ds_read_b64_tr_b16 for the
-// operand that is summed over its rows); a workgroup is four wavefronts and wave w owns rows 16 w .. 16 w + 15 of its 64-row block, as
+// depend on L.  The products, the operand layouts and the transposing LDS reads are the fragment layer of attn_frag.h
+// (v_mfma_f32_16x16x32_{f16,bf16}, scores computed TRANSPOSED so that the probabilities are already the B operand of the next product,
+// ds_read_b64_tr_b16 for the operand that is summed over its rows); a workgroup is four wavefronts and wave w owns rows 16 w .. 16 w + 15 of its 64-row block, as
 // in attn_bwd4_kernel.
 //
 // Forward, one workgroup per (image, head, 64-query block): for every 64-key block kb, in order, the K and V slabs go through two LDS
@@ -32,78 +32,12 @@
 // dbias (the in-projection bias gradient) keeps attn_bwd4_kernel's form: start + column sums, the Q third from the unrounded fp32 dQ, the
 // V third the column sums of dO (a softmax row sums to one), the K third exact zeros (a softmax-backward row sums to zero: start keeps
 // its bits); per-(image, head) partial rows in bias_scratch, then the fixed-order finish kernel.
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
 
-constexpr int ROWB = 160;            // LDS row pitch in bytes (64 x 16-bit + pad), as attention.hip
-constexpr int TILEB = 64 * ROWB;     // one 64 x 64 operand image
+using namespace attn_frag;       // the LDS image (ROWB, TILEB, rswz), the fragments, the reductions, store_row16
 constexpr int LPAD = (EOE_ATTN_LONG_MAX_L + 63) / 64 * 64;
-__device__ __forceinline__ int rswz(int row) { return (row & 1) << 4; }          // attention.hip: odd rows' 16-byte chunks pairwise swapped
-
-template <typename T> using V8 = typename T16<T>::v8;
-
-__device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, int row, int L, unsigned pitchb, unsigned cb) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(row < L ? (unsigned)row * pitchb + cb : EOE_OOB), 0, 0));
-}
-// row-major fragment of one row per lane & 15 (operand element j <-> column 8 * (lane >> 4) + j of k-step ks), zeros for row >= L
-template <typename T>
-__device__ __forceinline__ V8<T> rowfrag(__amdgpu_buffer_rsrc_t r, unsigned pitchb, unsigned cb0, int L, int row, int ks, int lane) {
-    return __builtin_bit_cast(V8<T>, bload16(r, row, L, pitchb, cb0 + (unsigned)(ks * 4 + (lane >> 4)) * 16u));
-}
-// the same fragment of 16-row tile t from an LDS image
-template <typename T>
-__device__ __forceinline__ V8<T> lfrag(const char* lds, int t, int ks, int lane) {
-    const int row = t * 16 + (lane & 15);
-    return __builtin_bit_cast(V8<T>, *(const u32x4*)(lds + row * ROWB + (((ks * 4 + (lane >> 4)) * 16) ^ rswz(row))));
-}
-// transposed fragment with the columns of the four tiles interleaved (attention.hip, tfrag_il): lane (lr, g) of result tile tc gets column
-// 16 g + 4 tc + 0..3; element j <-> row 32 s + 4 g + j (j < 4) / 32 s + 16 + 4 g + j - 4 (j >= 4), the order acc_as_operand produces
-template <typename T>
-__device__ __forceinline__ V8<T> tfrag_il(const char* lds, int tc, int s, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const char* a = lds + (32 * s + 4 * g + q) * ROWB + (((16 * p + 4 * tc) * 2) ^ rswz(4 * g + q));
-    i16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a));
-    i16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a + 16 * ROWB));
-    i16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return __builtin_bit_cast(V8<T>, r);
-}
-// two accumulator tiles (rows 32 s + 0..15 and 32 s + 16..31 of a transposed product) as the next B operand: the 16-bit rounding
-template <typename T>
-__device__ __forceinline__ V8<T> acc_as_operand(const f32x4& lo, const f32x4& hi) {
-    V8<T> r;
-    r[0] = (T)lo[0]; r[1] = (T)lo[1]; r[2] = (T)lo[2]; r[3] = (T)lo[3];
-    r[4] = (T)hi[0]; r[5] = (T)hi[1]; r[6] = (T)hi[2]; r[7] = (T)hi[3];
-    return r;
-}
-__device__ __forceinline__ float group_max(float v) {   // over the 4 lanes sharing lane & 15
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float group_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
-// column sums over the 16 tokens of one accumulator tile (token = lane & 15), in every lane of the DPP row (attention.hip, slab_sum)
-__device__ __forceinline__ f32x4 slab_sum(const f32x4& o, bool valid) {
-    f32x4 t = valid ? o : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float v = t[r];
-        v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
-        v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
-        v += dpp_mov<0x141>(v);     // row_half_mirror
-        v += dpp_mov<0x140>(v);     // row_mirror
-        t[r] = v;
-    }
-    return t;
-}
 
 // Two 64-row slabs (rows 64 blk .. 64 blk + 63 of two operands) on their way into two LDS images: wave w moves rows 16 w .. 16 w + 15,
 // a lane 16 bytes of two rows per operand.  load() only issues the reads; store() waits for every wave to be done with the images' old
@@ -206,11 +140,7 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const T* __restrict_
     u32x2 pk[4];
 #pragma unroll
     for (int td = 0; td < 4; ++td) pk[td] = pack4<T>(o[td][0] * inv, o[td][1] * inv, o[td][2] * inv, o[td][3] * inv);
-    if (mine < L) {
-        T* d = out + ((size_t)img * L + mine) * D + h * 64 + 16 * lg;
-        *(u32x4*)d = (u32x4){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
-        *(u32x4*)(d + 8) = (u32x4){pk[2][0], pk[2][1], pk[3][0], pk[3][1]};
-    }
+    if (mine < L) store_row16(out + ((size_t)img * L + mine) * D + h * 64 + 16 * lg, pk);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -345,11 +275,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_kernel(const T* __restrict_
             pk[td] = pack4<T>(o[td][0], o[td][1], o[td][2], o[td][3]);
             csq[td] += slab_sum(o[td], mine < L);
         }
-        if (mine < L) {
-            T* d = dqp + (size_t)mine * ld + 16 * lg;
-            *(u32x4*)d = (u32x4){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
-            *(u32x4*)(d + 8) = (u32x4){pk[2][0], pk[2][1], pk[3][0], pk[3][1]};
-        }
+        if (mine < L) store_row16(dqp + (size_t)mine * ld + 16 * lg, pk);
     }
 
     // ---- phase B: lane = key (operands swapped).  S = Q K^T, dP = dO V^T; rows (registers) = queries
@@ -425,10 +351,8 @@ __global__ __launch_bounds__(256) void attn_long_bwd_kernel(const T* __restrict_
             }
             T* dv = dqp + (size_t)mine * ld + 2 * D + 16 * lg;
             T* dk = dqp + (size_t)mine * ld + D + 16 * lg;
-            *(u32x4*)dv = (u32x4){pv[0][0], pv[0][1], pv[1][0], pv[1][1]};
-            *(u32x4*)(dv + 8) = (u32x4){pv[2][0], pv[2][1], pv[3][0], pv[3][1]};
-            *(u32x4*)dk = (u32x4){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
-            *(u32x4*)(dk + 8) = (u32x4){pk[2][0], pk[2][1], pk[3][0], pk[3][1]};
+            store_row16(dv, pv);
+            store_row16(dk, pk);
         }
     }
     if (bpart) {

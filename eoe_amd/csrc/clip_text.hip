@@ -5,65 +5,17 @@
 //   * a LayerNorm over rows of any width D % 64 == 0 (eoe_layernorm_fwd serves D % 256 == 0 only).
 // The layer chain itself (LayerNorm, GEMMs with their epilogues) is eoe_clip_text_fwd in clip_text_driver.cpp.
 //
-// Attention: one wavefront per (sequence, head, 64-query block).  The products follow attn_fwd_kernel (attention.hip): scores are
-// computed TRANSPOSED (S^T = K Q^T, key on the accumulator row, query on the lane), so the probabilities are already the B operand of
+// Attention: one wavefront per (sequence, head, 64-query block).  The products follow attn_fwd_kernel (attention.hip) on the fragment
+// layer of attn_frag.h (LDS image, bounds-checked loads, operand fragments, lane-group reductions): scores are computed TRANSPOSED (S^T = K Q^T, key on the accumulator row, query on the lane), so the probabilities are already the B operand of
 // O^T = V^T P^T, with V read back through ds_read_b64_tr_b16 from an LDS image.  A query block visits the key blocks kb <= qb only (the
 // blocks above the diagonal are skipped) with an online softmax across them; keys j > i inside the diagonal block get -inf, so they
 // add exact zeros to the row sum and to the output.  Q, K and V rows >= L are read through a bounds-checked buffer resource as zeros,
 // and output rows >= L are not stored.
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
 
-constexpr int ROWB = 160;            // LDS row pitch in bytes (64 x 16-bit + pad), as attention.hip
-constexpr int TILEB = 64 * ROWB;     // one 64 x 64 operand image
-__device__ __forceinline__ int rswz(int row) { return (row & 1) << 4; }
-
-template <typename T> using V8 = typename T16<T>::v8;
-
-__device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, int row, int L, unsigned pitchb, unsigned cb) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(row < L ? (unsigned)row * pitchb + cb : EOE_OOB), 0, 0));
-}
-// row-major fragment of 16-row tile t, k-step ks (operand element j <-> column 8*(lane>>4)+j of the k-step); cb0 = byte offset of the
-// operand's head slice inside a row
-template <typename T>
-__device__ __forceinline__ V8<T> bfrag(__amdgpu_buffer_rsrc_t r, unsigned pitchb, unsigned cb0, int L, int t, int ks, int lane) {
-    return __builtin_bit_cast(V8<T>, bload16(r, t * 16 + (lane & 15), L, pitchb, cb0 + (unsigned)(ks * 4 + (lane >> 4)) * 16u));
-}
-// transposed fragment of the V image with the columns of the four d-tiles interleaved (attention.hip, tfrag_il): lane (lr, g) of result
-// tile td gets d = 16 g + 4 td + 0..3; element j <-> key 32 s + 4 g + j (j < 4) / 32 s + 16 + 4 g + j - 4 (j >= 4)
-template <typename T>
-__device__ __forceinline__ V8<T> tfrag_il(const char* lds, int tc, int s, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const char* a = lds + (32 * s + 4 * g + q) * ROWB + (((16 * p + 4 * tc) * 2) ^ rswz(4 * g + q));
-    i16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a));
-    i16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4v*)(a + 16 * ROWB));
-    i16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return __builtin_bit_cast(V8<T>, r);
-}
-// two accumulator tiles (keys 32s+0..15 and 32s+16..31 of the transposed scores) as the B operand of O^T = V^T P^T
-template <typename T>
-__device__ __forceinline__ V8<T> acc_as_operand(const f32x4& lo, const f32x4& hi) {
-    V8<T> r;
-    r[0] = (T)lo[0]; r[1] = (T)lo[1]; r[2] = (T)lo[2]; r[3] = (T)lo[3];
-    r[4] = (T)hi[0]; r[5] = (T)hi[1]; r[6] = (T)hi[2]; r[7] = (T)hi[3];
-    return r;
-}
-__device__ __forceinline__ float group_max(float v) {   // over the 4 lanes sharing lane&15 (one query)
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float group_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-
-// one resource over rows [r0, r0 + Lb) of a sequence's packed Q | K | V, rooted at head h's Q slice (the last row ends behind V's 64 columns)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t block_rsrc(const void* qkv_row0, int Lb, int ld, int D) {
-    return make_rsrc(qkv_row0, ((unsigned)(Lb - 1) * (unsigned)ld + 2u * (unsigned)D + 64u) * 2u);
-}
+using namespace attn_frag;       // the LDS image (ROWB, TILEB, rswz), the fragments, the reductions, qkv_rsrc, store_row16
 
 template <typename T>
 __global__ __launch_bounds__(64) void attn_causal_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out, int L, int heads, int nqb,
@@ -79,7 +31,7 @@ __global__ __launch_bounds__(64) void attn_causal_fwd_kernel(const T* __restrict
     const T* base = qkv + (size_t)seq * L * ld + h * 64;
 
     const int Lq = min(64, L - qb * 64);
-    const __amdgpu_buffer_rsrc_t rq = block_rsrc(base + (size_t)qb * 64 * ld, Lq, ld, D);
+    const __amdgpu_buffer_rsrc_t rq = qkv_rsrc(base + (size_t)qb * 64 * ld, Lq, ld, D);
     V8<T> qf[2][4];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -97,7 +49,7 @@ __global__ __launch_bounds__(64) void attn_causal_fwd_kernel(const T* __restrict
 
     for (int kb = 0; kb <= qb; ++kb) {
         const int Lk = min(64, L - kb * 64);
-        const __amdgpu_buffer_rsrc_t rk = block_rsrc(base + (size_t)kb * 64 * ld, Lk, ld, D);
+        const __amdgpu_buffer_rsrc_t rk = qkv_rsrc(base + (size_t)kb * 64 * ld, Lk, ld, D);
         char* vimg = vs[kb];
         u32x4 vv[8];
 #pragma unroll
@@ -175,11 +127,7 @@ __global__ __launch_bounds__(64) void attn_causal_fwd_kernel(const T* __restrict
         u32x2 pk[4];
 #pragma unroll
         for (int td = 0; td < 4; ++td) pk[td] = pack4<T>(o[td][tq][0] * inv, o[td][tq][1] * inv, o[td][tq][2] * inv, o[td][tq][3] * inv);
-        if (query < Lq) {
-            T* d = out + ((size_t)seq * L + qb * 64 + query) * D + h * 64 + 16 * lg;
-            *(u32x4*)d = (u32x4){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
-            *(u32x4*)(d + 8) = (u32x4){pk[2][0], pk[2][1], pk[3][0], pk[3][1]};
-        }
+        if (query < Lq) store_row16(out + ((size_t)seq * L + qb * 64 + query) * D + h * 64 + 16 * lg, pk);
     }
 }
 
