@@ -20,6 +20,12 @@ EOE_MSM_FORM_NONE, EOE_MSM_FORM_DENSE, EOE_MSM_FORM_RANK = 0, 1, 2
 EOE_GCN_L1, EOE_GCN_L2 = 1, 2
 EOE_COMM_I64, EOE_COMM_ID_BYTES, EOE_COMM_ALGO_RING, EOE_COMM_ALGO_RS_AG = 8, 128, 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD = 0, 1, 2, 3
+# EOE_NT_KERNEL_* (get_option("nt_last_kernel"): the route the last eoe_gemm_nt took; read-only diagnostics)
+NT_KERNELS = ("none", "persistent_256x128", "persistent_256x96", "narrow_256x64", "persistent_narrow", "two_wg_128", "two_wg_160",
+              "wide_160x256x32", "one_wave_160x256", "one_wave_256x256", "eight_wave", "eight_wave_stream_k", "split_k", "gather")
+(NT_KERNEL_NONE, NT_KERNEL_PERSISTENT_256x128, NT_KERNEL_PERSISTENT_256x96, NT_KERNEL_NARROW_256x64, NT_KERNEL_PERSISTENT_NARROW,
+ NT_KERNEL_TWO_WG_128, NT_KERNEL_TWO_WG_160, NT_KERNEL_WIDE_160x256x32, NT_KERNEL_ONE_WAVE_160x256, NT_KERNEL_ONE_WAVE_256x256,
+ NT_KERNEL_EIGHT_WAVE, NT_KERNEL_EIGHT_WAVE_STREAM_K, NT_KERNEL_SPLIT_K, NT_KERNEL_GATHER) = range(14)
 ADAM_CHUNK, ADAM_GROUPS = 8192, 4
 CHUNK_FP16 = 0x100                 # eoe_adam_chunk.group flag (EOE_CHUNK_FP16): fp16-weights update in eoe_sgd_multi
 EOE_Y16 = 0x100             # OR-ed into the dtype argument of eoe_bn_act_*: y is the 16-bit copy (include/eoe_hip.h)

@@ -30,6 +30,7 @@ extern int g_tn_flags;     // gemm_tn.hip
 extern int g_vit_side_stream;   // vit.cpp
 extern int g_attn_flags;        // attention.hip
 extern int g_tn256_launches;    // gemm_tn256.hip
+int g_nt_last_kernel = EOE_NT_KERNEL_NONE;      // diagnostics: eoe_get_option("nt_last_kernel"), the route of the last eoe_gemm_nt (host side only)
 extern int g_parity_flags;      // parity.hip
 int eoe_launch_nt256(const void* gemm_p, int dtype, int epi, int mi, hipStream_t s);   // gemm256.hip
 bool eoe_w8_applies(const void* gemm_p, int epi);                                       // gemm_w8.hip
@@ -771,6 +772,7 @@ template <typename T, int GATHER>
 int launch_nt64(const GemmP& p, hipStream_t s) {
     static bool once = (hipFuncSetAttribute((const void*)gemm_nt64_kernel<T, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM64_BYTES), true);
     (void)once;
+    g_nt_last_kernel = GATHER ? EOE_NT_KERNEL_GATHER : EOE_NT_KERNEL_NARROW_256x64;
     hipLaunchKernelGGL((gemm_nt64_kernel<T, GATHER>), dim3(cdiv(p.M, 256)), dim3(256), SMEM64_BYTES, s, p);
     EOE_CHECK_LAUNCH("gemm_nt64");
     return 0;
@@ -782,6 +784,7 @@ int launch_nt128_gather(const GemmP& p, hipStream_t s) {
     const int tiles = cdiv(p.M, 32 * MI) * cdiv(p.N, 128);
     static bool once = (hipFuncSetAttribute((const void*)gemm_nt128_kernel<T, EOE_EPI_NONE, MI, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem128_bytes(MI)), true);
     (void)once;
+    g_nt_last_kernel = EOE_NT_KERNEL_GATHER;
     hipLaunchKernelGGL((gemm_nt128_kernel<T, EOE_EPI_NONE, MI, 1>), dim3(tiles), dim3(256), smem128_bytes(MI), s, p);
     EOE_CHECK_LAUNCH("gemm_nt128 (gather)");
     return finish_colsum(p, EOE_EPI_NONE, MI, s);
@@ -790,6 +793,7 @@ int launch_nt128_gather(const GemmP& p, hipStream_t s) {
 template <typename T, int MI>
 int launch_nt128(const GemmP& p, int epi, hipStream_t s) {
     const int tiles = cdiv(p.M, 32 * MI) * cdiv(p.N, 128);
+    g_nt_last_kernel = MI == 5 ? EOE_NT_KERNEL_TWO_WG_160 : EOE_NT_KERNEL_TWO_WG_128;
 #define EOE_NT128_CASE(E)                                                                   \
     case E:                                                                                 \
         { static bool once = (hipFuncSetAttribute((const void*)gemm_nt128_kernel<T, E, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem128_bytes(MI)), true); (void)once; } \
@@ -810,6 +814,7 @@ int launch_nt128(const GemmP& p, int epi, hipStream_t s) {
 template <typename T>
 int launch_nt128w(const GemmP& p, int epi, hipStream_t s) {
     const int tiles = cdiv(p.M, 160) * cdiv(p.N, 256);
+    g_nt_last_kernel = EOE_NT_KERNEL_WIDE_160x256x32;
 #define EOE_NT128W_CASE(E)                                                                  \
     case E:                                                                                 \
         { static bool once = (hipFuncSetAttribute((const void*)gemm_nt128w_kernel<T, E>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEMW_BYTES), true); (void)once; } \
@@ -877,6 +882,7 @@ int launch_nt128_splitk(const GemmP& p, int epi, hipStream_t s) {
     GemmP q = p;
     q.C = part; q.ldc = p.N; q.out_f32 = 1; q.bias = nullptr; q.aux = nullptr; q.alpha = 1.0f;
     const int tiles = cdiv(p.M, 128) * cdiv(p.N, 128);
+    g_nt_last_kernel = EOE_NT_KERNEL_SPLIT_K;
     { static bool once = (hipFuncSetAttribute((const void*)gemm_nt128_kernel<T, EOE_EPI_NONE, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem128_bytes(4)), true); (void)once; }
     hipLaunchKernelGGL((gemm_nt128_kernel<T, EOE_EPI_NONE, 4>), dim3(tiles, S), dim3(256), smem128_bytes(4), s, q);
     EOE_CHECK_LAUNCH("gemm_nt128 (split k)");
@@ -915,6 +921,7 @@ int g_nt_flags = EOE_NT_DEFAULT_FLAGS;
 
 template <typename T, int NI, int FLAGS>
 int launch_nt_f(const GemmP& p, int epi, int grid, hipStream_t s) {
+    g_nt_last_kernel = NI == 3 ? EOE_NT_KERNEL_PERSISTENT_256x96 : EOE_NT_KERNEL_PERSISTENT_256x128;
 #define EOE_NT_CASE(E)                                                                      \
     case E:                                                                                 \
         { static bool once = (hipFuncSetAttribute((const void*)gemm_nt_kernel<T, E, NI, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES), true); (void)once; } \
@@ -938,6 +945,7 @@ int launch_nt_conv(const GemmP& p, int grid, hipStream_t s) {
     static bool once = (hipFuncSetAttribute((const void*)gemm_nt_kernel<T, EOE_EPI_NONE, NI, EOE_NT_DEFAULT_FLAGS, GATHER>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES), true);
     (void)once;
+    g_nt_last_kernel = GATHER ? EOE_NT_KERNEL_GATHER : EOE_NT_KERNEL_PERSISTENT_NARROW;
     hipLaunchKernelGGL((gemm_nt_kernel<T, EOE_EPI_NONE, NI, EOE_NT_DEFAULT_FLAGS, GATHER>), dim3(grid), dim3(512), SMEM_BYTES, s, p);
     EOE_CHECK_LAUNCH("gemm_nt");
     return finish_colsum(p, EOE_EPI_NONE, 4, s);
@@ -990,8 +998,10 @@ int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
     // 83 -> 68 us = 887 TF, K = 2304: 61 -> 50 us = 916 TF).  The persistent 256-row kernel keeps large square problems
     // (4096^3: 1046 vs 984 TF).  nt_flags: bit 3 forces the two-workgroup kernel, bit 2 forbids it, bit 4 / 5 force 128 / 160 rows.
     // the one-wave-per-SIMD kernel (gemm256.hip) has only the LDS-transposed epilogue compiled in
-    if ((g_nt_flags & (128 | 256)) && epilogue_direct_ok(p, epi))
+    if ((g_nt_flags & (128 | 256)) && epilogue_direct_ok(p, epi)) {
+        g_nt_last_kernel = (g_nt_flags & 256) ? EOE_NT_KERNEL_ONE_WAVE_256x256 : EOE_NT_KERNEL_ONE_WAVE_160x256;
         return eoe_launch_nt256(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, (g_nt_flags & 256) ? 8 : 5, s);
+    }
     const bool big = p.K >= 4096 && p.N >= 2048;
     // The one-wave-per-SIMD kernel (gemm256.hip; 160x256 or 256x256 tiles by the cost model below) for every large NT GEMM: OPT-IN
     // (nt_flags bit 9 = 512).  Stand-alone at M = 12800 (tools/gemm_bench.py, the same GEMM back to back, operands hot in the
@@ -1018,8 +1028,10 @@ int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
         // (round 5) opt-in, nt_flags bit 20 = 1048576: with the caller's stream-K workspace the fractional last round is cut along k over all
         // CUs (bit 21: the last full round joins the stream-K part; bit 22: stream-K part first).  Measured slower than the rules below on every
         // ViT shape (gemm_w8.hip, w8_sk_rounds)
-        if ((g_nt_flags & 262144) || eoe_w8_streamk(&p) || tiles * 100 >= ((tiles + ncu - 1) / ncu) * ncu * 85) 
+        if ((g_nt_flags & 262144) || eoe_w8_streamk(&p) || tiles * 100 >= ((tiles + ncu - 1) / ncu) * ncu * 85) {
+            g_nt_last_kernel = eoe_w8_streamk(&p) ? EOE_NT_KERNEL_EIGHT_WAVE_STREAM_K : EOE_NT_KERNEL_EIGHT_WAVE;
             return eoe_launch_w8(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, s);
+        }
     }
     // the 160x256x32 two-workgroup kernel on the wide-N shapes (c_fc forward, GELU' x dY: 10.64 -> 10.54 ms per step, three interleaved
     // pairs, same bits; nt_flags bit 12 = 4096 switches it off)
@@ -1040,10 +1052,13 @@ int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
             const long cost = ((tiles + ncu - 1) / ncu) * ((long)mi * (nk + 2) + 30);
             if (!best || cost < best) { best = cost; mi_best = mi; }
         }
+        g_nt_last_kernel = mi_best == 8 ? EOE_NT_KERNEL_ONE_WAVE_256x256 : EOE_NT_KERNEL_ONE_WAVE_160x256;
         return eoe_launch_nt256(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, mi_best, s);
     }
-    if (big && !(g_nt_flags & (4 | 8)) && epilogue_direct_ok(p, epi) && p.M >= 2048)
+    if (big && !(g_nt_flags & (4 | 8)) && epilogue_direct_ok(p, epi) && p.M >= 2048) {
+        g_nt_last_kernel = EOE_NT_KERNEL_ONE_WAVE_256x256;
         return eoe_launch_nt256(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, 8, s);
+    }
     if (!p.colsum_sq && ((g_nt_flags & 8) || (!big && !(g_nt_flags & 4)))) return launch_nt128_auto<T>(p, epi, s);
     // tile width: 256x128 unless 256x96 needs >= 10 % fewer (rounds x width) units over the CUs
     const int t4 = cdiv(p.M, BM) * cdiv(p.N, 128), t3 = cdiv(p.M, BM) * cdiv(p.N, 96);
@@ -1192,6 +1207,7 @@ extern "C" int eoe_get_option(const char* name, int* value) {
     if (!strcmp(name, "vit_side_stream")) { *value = g_vit_side_stream; return 0; }
     if (!strcmp(name, "attn_flags")) { *value = g_attn_flags; return 0; }
     if (!strcmp(name, "tn256_launches")) { *value = g_tn256_launches; return 0; }       // read-only diagnostics
+    if (!strcmp(name, "nt_last_kernel")) { *value = g_nt_last_kernel; return 0; }       // read-only diagnostics: EOE_NT_KERNEL_*
     if (!strcmp(name, "parity_flags")) { *value = g_parity_flags; return 0; }
     return eoe_set_error(EOE_ERR_ARG, "unknown option");
 }

@@ -1024,6 +1024,24 @@ int eoe_probe_copy(void* dst, const void* src, int64_t bytes, void* stream);
 /* tuning switches for A/B measurements inside one process ("nt_flags": see gemm.hip) */
 int eoe_set_option(const char* name, int value);
 int eoe_get_option(const char* name, int* value);    /* the current value (callers that change a switch restore what they found) */
+/* "nt_last_kernel" (read-only diagnostics, like "tn256_launches"): the route the last eoe_gemm_nt of this process took, set on the host by the
+ * launcher; tests assert it so that a case which falls through to another kernel fails instead of passing */
+enum {
+    EOE_NT_KERNEL_NONE = 0,                  /* no NT GEMM launched yet */
+    EOE_NT_KERNEL_PERSISTENT_256x128 = 1,    /* gemm.hip: eight waves, one workgroup per CU, 256 x 128 tiles */
+    EOE_NT_KERNEL_PERSISTENT_256x96 = 2,     /*           the same with 256 x 96 tiles */
+    EOE_NT_KERNEL_NARROW_256x64 = 3,         /*           N <= 64: 256 x 64 tiles, two workgroups per CU */
+    EOE_NT_KERNEL_PERSISTENT_NARROW = 4,     /*           N <= 64: the persistent kernel with 256 x 64 tiles */
+    EOE_NT_KERNEL_TWO_WG_128 = 5,            /*           two workgroups per CU, 128 x 128 tiles */
+    EOE_NT_KERNEL_TWO_WG_160 = 6,            /*           two workgroups per CU, 160 x 128 tiles */
+    EOE_NT_KERNEL_WIDE_160x256x32 = 7,       /*           two workgroups per CU, 160 x 256 tiles, 32-deep k-tiles */
+    EOE_NT_KERNEL_ONE_WAVE_160x256 = 8,      /* gemm256.hip: one wave per SIMD, 160 x 256 tiles */
+    EOE_NT_KERNEL_ONE_WAVE_256x256 = 9,      /*              one wave per SIMD, 256 x 256 tiles */
+    EOE_NT_KERNEL_EIGHT_WAVE = 10,           /* gemm_w8.hip: eight waves, 256 x 256 tiles, data-parallel */
+    EOE_NT_KERNEL_EIGHT_WAVE_STREAM_K = 11,  /*              its stream-K form */
+    EOE_NT_KERNEL_SPLIT_K = 12,              /* gemm.hip: split k (eoe_gemm_args.split_k) + the in-order finish kernel */
+    EOE_NT_KERNEL_GATHER = 13                /* any implicit-convolution (gather != 0) form */
+};
 /* diagnostics only (EOE_GEMM_STAMP=1): in-kernel s_memtime stamps of the last eoe_gemm_nt launch, 16 words per workgroup */
 int eoe_debug_gemm_stamps(unsigned long long* out, int n_words);
 int eoe_prof_collect(eoe_prof_entry* out, int max_entries, int* n_out);

@@ -32,6 +32,23 @@ NT_VARIANTS = {"auto": 1, "persistent256": 1 | 4 | 64, "two_wg_128": 1 | 8 | 16,
 
 @pytest.fixture(params=list(NT_VARIANTS))
 def nt_variant(request):
+    """sets nt_flags for one test.  The flags are a request: below M = 2048 launch_nt ignores several bits, and a parametrisation then
+    runs the default route under another name (read from gemm.hip; on 256 CUs).  At the shapes of test_gemm_nt_plain and at
+    (200, 256, 128) of test_gemm_nt_strided_and_epilogues:
+      * eight_wave, eight_wave_stream_k: the two-workgroup 128-row kernel at every shape with N > 64 except (12800, 768, 768), where
+        only the 16-bit launch is the eight-wave kernel's (the fp32 and accumulate launches run two-workgroup 160-row tiles)
+      * halves_off, nt128w_old_image: never their 160 x 256 x 32 kernel (no N >= 2048 here): what `auto` runs, at every shape
+      * one_wave_cost_model: its kernel only at (12800, 768, 768); the two-workgroup 128-row kernel elsewhere
+      * one_wave_160x256, one_wave_256x256: the two-workgroup 128-row kernel at (130, 136, 64), (161, 264, 64), (480, 136, 256)
+        (N % 16 != 0: epilogue_direct_ok refuses)
+      * every variant but persistent256: the 256 x 64 narrow kernel at (50, 8, 64), (1000, 64, 192), (300, 48, 64) -- the N <= 64 rule
+        precedes the others, so two_wg_128 and two_wg_160 never run there (persistent256: the persistent narrow kernel)
+    These parametrisations stay; the rows of tests/gemm_util.nt_table that cover each variant for real, asserting the route taken
+    (`nt_last_kernel`), are: eight_wave -> "eight_wave"; halves_off / nt128w_old_image / the rule itself -> "wide_160x256x32" (the two
+    A/B bits keep test_gemm_nt_wide_kernel_tile_order_and_image); one_wave_* -> "one_wave_160x256", "one_wave_256x256" (the cost
+    model picks between these two kernels); two_wg_* -> "two_wg_128", "two_wg_160"; persistent256 -> "persistent_256x128",
+    "persistent_256x96", "persistent_narrow"; auto at N <= 64 -> "narrow_256x64"; the opt-in stream-K form keeps
+    test_gemm_nt_eight_wave and test_gpu_round5"""
     from eoe_amd import _lib
     _lib.check(_lib.lib.eoe_set_option(b"nt_flags", NT_VARIANTS[request.param]), "eoe_set_option")
     yield request.param
