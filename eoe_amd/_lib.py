@@ -151,6 +151,7 @@ SIGNATURES = {
     "eoe_vit_side_join": [_vp],
     "eoe_red_table_flush": [C.POINTER(RedTable), _vp],
     "eoe_gemm_nt": [C.POINTER(GemmArgs), _vp],
+    "eoe_gemm_nt_route": [C.POINTER(GemmArgs), C.c_int, C.POINTER(C.c_int)],
     "eoe_gemm_tn": [C.POINTER(GemmArgs), _vp],
     "eoe_gemm_tn_grouped": [C.POINTER(GemmArgs), C.c_int, _vp],
     "eoe_cast_transpose": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
@@ -331,6 +332,14 @@ def set_option(name: str, value: int) -> int:
     old = get_option(name)
     check(lib.eoe_set_option(name.encode(), int(value)), "eoe_set_option")
     return old
+
+
+def gemm_nt_route(args: GemmArgs, ncu: int = 0) -> int:
+    """the route (an index into NT_KERNELS) eoe_gemm_nt would take with `args` and the current nt_flags on `ncu` CUs (0: the current
+    device's); launches nothing, and with ncu > 0 needs no GPU"""
+    v = C.c_int(0)
+    check(lib.eoe_gemm_nt_route(C.byref(args), int(ncu), C.byref(v)), "eoe_gemm_nt_route")
+    return v.value
 
 
 lib = _load()

@@ -21,9 +21,6 @@
 // loads/stores are 8-B (16-bit) or 16-B (fp32) vectors along the contiguous dimension.
 #include "gemm_common.h"
 #include <stdlib.h>
-#include <map>
-#include <mutex>
-#include <type_traits>
 
 unsigned long long* g_stamp_buf = nullptr;
 extern int g_tn_flags;     // gemm_tn.hip
@@ -32,13 +29,12 @@ extern int g_attn_flags;        // attention.hip
 extern int g_tn256_launches;    // gemm_tn256.hip
 int g_nt_last_kernel = EOE_NT_KERNEL_NONE;      // diagnostics: eoe_get_option("nt_last_kernel"), the route of the last eoe_gemm_nt (host side only)
 extern int g_parity_flags;      // parity.hip
-int eoe_launch_nt256(const void* gemm_p, int dtype, int epi, int mi, hipStream_t s);   // gemm256.hip
+template <typename T> int eoe_launch_nt256(const void* gemm_p, int epi, int mi, hipStream_t s);   // gemm256.hip
 bool eoe_w8_applies(const void* gemm_p, int epi);                                       // gemm_w8.hip
-int eoe_launch_w8(const void* gemm_p, int dtype, int epi, hipStream_t s);
-bool eoe_w8_streamk(const void* gemm_p);                                                // would run in its stream-K form (caller's workspace)
+int eoe_w8_sk_rounds(const void* gemm_p, int flags, int ncu);                           // its stream-K plan (caller's workspace), -1: data-parallel
+template <typename T> int eoe_launch_w8(const void* gemm_p, int epi, int sk_rounds, hipStream_t s);
 
 namespace {
-extern int g_nt_flags;
 
 // ------------------------------------------------------------------------------------------------ NT
 // main loop: 3-stage LDS ring filled by LDS-DMA two k-tiles ahead (counted vmcnt: the newest tile stays in
@@ -770,22 +766,16 @@ __global__ __launch_bounds__(256, 2) void gemm_nt64_kernel(GemmP p) {
 
 template <typename T, int GATHER>
 int launch_nt64(const GemmP& p, hipStream_t s) {
-    static bool once = (hipFuncSetAttribute((const void*)gemm_nt64_kernel<T, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM64_BYTES), true);
-    (void)once;
-    g_nt_last_kernel = GATHER ? EOE_NT_KERNEL_GATHER : EOE_NT_KERNEL_NARROW_256x64;
-    hipLaunchKernelGGL((gemm_nt64_kernel<T, GATHER>), dim3(cdiv(p.M, 256)), dim3(256), SMEM64_BYTES, s, p);
+    launch_gemm<gemm_nt64_kernel<T, GATHER>>(dim3(cdiv(p.M, 256)), dim3(256), SMEM64_BYTES, s, p);
     EOE_CHECK_LAUNCH("gemm_nt64");
-    return 0;
+    return finish_colsum(p, EOE_EPI_NONE, 4, s);
 }
 
 // the implicit-convolution form (plain epilogue, optional BatchNorm statistics for MI = 4: 64 output rows per wave = the partial rows' unit)
 template <typename T, int MI>
 int launch_nt128_gather(const GemmP& p, hipStream_t s) {
     const int tiles = cdiv(p.M, 32 * MI) * cdiv(p.N, 128);
-    static bool once = (hipFuncSetAttribute((const void*)gemm_nt128_kernel<T, EOE_EPI_NONE, MI, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem128_bytes(MI)), true);
-    (void)once;
-    g_nt_last_kernel = EOE_NT_KERNEL_GATHER;
-    hipLaunchKernelGGL((gemm_nt128_kernel<T, EOE_EPI_NONE, MI, 1>), dim3(tiles), dim3(256), smem128_bytes(MI), s, p);
+    launch_gemm<gemm_nt128_kernel<T, EOE_EPI_NONE, MI, 1>>(dim3(tiles), dim3(256), smem128_bytes(MI), s, p);
     EOE_CHECK_LAUNCH("gemm_nt128 (gather)");
     return finish_colsum(p, EOE_EPI_NONE, MI, s);
 }
@@ -793,20 +783,9 @@ int launch_nt128_gather(const GemmP& p, hipStream_t s) {
 template <typename T, int MI>
 int launch_nt128(const GemmP& p, int epi, hipStream_t s) {
     const int tiles = cdiv(p.M, 32 * MI) * cdiv(p.N, 128);
-    g_nt_last_kernel = MI == 5 ? EOE_NT_KERNEL_TWO_WG_160 : EOE_NT_KERNEL_TWO_WG_128;
-#define EOE_NT128_CASE(E)                                                                   \
-    case E:                                                                                 \
-        { static bool once = (hipFuncSetAttribute((const void*)gemm_nt128_kernel<T, E, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem128_bytes(MI)), true); (void)once; } \
-        hipLaunchKernelGGL((gemm_nt128_kernel<T, E, MI>), dim3(tiles), dim3(256), smem128_bytes(MI), s, p); \
-        break;
-    switch (epi) {
-        EOE_NT128_CASE(EOE_EPI_NONE)
-        EOE_NT128_CASE(EOE_EPI_GELU)
-        EOE_NT128_CASE(EOE_EPI_RESIDUAL)
-        EOE_NT128_CASE(EOE_EPI_GELU_BWD)
-        default: return eoe_set_error(EOE_ERR_ARG, "gemm_nt: unknown epilogue %d", epi);
-    }
-#undef EOE_NT128_CASE
+    EOE_TRY(for_epilogue<EOE_ALL_EPILOGUES>(epi, [&](auto E) {
+        launch_gemm<gemm_nt128_kernel<T, decltype(E)::value, MI>>(dim3(tiles), dim3(256), smem128_bytes(MI), s, p);
+    }));
     EOE_CHECK_LAUNCH("gemm_nt128");
     return finish_colsum(p, epi, MI, s);
 }
@@ -814,34 +793,11 @@ int launch_nt128(const GemmP& p, int epi, hipStream_t s) {
 template <typename T>
 int launch_nt128w(const GemmP& p, int epi, hipStream_t s) {
     const int tiles = cdiv(p.M, 160) * cdiv(p.N, 256);
-    g_nt_last_kernel = EOE_NT_KERNEL_WIDE_160x256x32;
-#define EOE_NT128W_CASE(E)                                                                  \
-    case E:                                                                                 \
-        { static bool once = (hipFuncSetAttribute((const void*)gemm_nt128w_kernel<T, E>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEMW_BYTES), true); (void)once; } \
-        hipLaunchKernelGGL((gemm_nt128w_kernel<T, E>), dim3(tiles), dim3(256), SMEMW_BYTES, s, p); \
-        break;
-    switch (epi) {
-        EOE_NT128W_CASE(EOE_EPI_NONE)
-        EOE_NT128W_CASE(EOE_EPI_GELU)
-        EOE_NT128W_CASE(EOE_EPI_RESIDUAL)
-        EOE_NT128W_CASE(EOE_EPI_GELU_BWD)
-        default: return eoe_set_error(EOE_ERR_ARG, "gemm_nt: unknown epilogue %d", epi);
-    }
-#undef EOE_NT128W_CASE
+    EOE_TRY(for_epilogue<EOE_ALL_EPILOGUES>(epi, [&](auto E) {
+        launch_gemm<gemm_nt128w_kernel<T, decltype(E)::value>>(dim3(tiles), dim3(256), SMEMW_BYTES, s, p);
+    }));
     EOE_CHECK_LAUNCH("gemm_nt128w");
     return finish_colsum(p, epi, 5, s);
-}
-
-// 128- or 160-row tiles: whichever needs less (rounds over the 2 x #CU workgroup slots) x (rows per tile)
-template <typename T>
-int launch_nt128_auto(const GemmP& p, int epi, hipStream_t s) {
-    const int slots = 2 * num_cus();
-    const long t4 = (long)cdiv(p.M, 128) * cdiv(p.N, 128), t5 = (long)cdiv(p.M, 160) * cdiv(p.N, 128);
-    const long c4 = (t4 + slots - 1) / slots * 128, c5 = (t5 + slots - 1) / slots * 160;
-    // (a tie goes to the 160-row tiles: N = 3072 at M = 12800 is 5 x 128 = 4 x 160 rounds x rows, and the in-step timing of
-    //  tools/nt_shapes_sweep.sh has GELU' x dY at 1.226 against 1.260 ms per step with them -- fewer, larger tiles per slot)
-    const bool five = (g_nt_flags & 32) || (!(g_nt_flags & 16) && c5 <= c4);
-    return five ? launch_nt128<T, 5>(p, epi, s) : launch_nt128<T, 4>(p, epi, s);
 }
 
 // ---- split k for small M behind a long K, on request (eoe_gemm_args.split_k; round 3: the last ViT block on its class-token rows: 256 x 768 x
@@ -867,24 +823,14 @@ __global__ __launch_bounds__(256) void nt_splitk_finish_kernel(const float* __re
 
 // (round 5) the partial tiles live in the CALLER's workspace -- the slot area of eoe_gemm_args.sk_workspace -- and no longer in a library-owned
 // buffer grown with hipMalloc / hipStreamSynchronize / hipFree: nothing the caller's allocator, a graph capture or a second process cannot see
-// returns -1 when the split form does not apply (the caller then takes the plain launch)
+// S: the k-ranges per tile (nt_split_s)
 template <typename T>
-int launch_nt128_splitk(const GemmP& p, int epi, hipStream_t s) {
-    const int nk = p.K / BK;
-    if ((g_nt_flags & 8192) || !p.split_k || p.M > 1024 || nk < 24 || (epi != EOE_EPI_NONE && epi != EOE_EPI_RESIDUAL) || p.colsum || p.colsum_sq || p.accumulate ||
-        (p.N & 15) || (p.ldc & 3) || (epi == EOE_EPI_RESIDUAL && (p.ldaux & 3)))
-        return -1;
-    int S = 8;
-    while (S > 1 && (nk % S) != 0) S >>= 1;
-    if (S < 2 || nk / S < 3) return -1;
+int launch_nt128_splitk(const GemmP& p, int epi, int S, hipStream_t s) {
     float* part = p.sk_part;                          // 2 x #CUs slots of 256 x 256 floats
-    if (!part || (size_t)S * p.M * p.N > (size_t)2 * num_cus() * 65536) return -1;
     GemmP q = p;
     q.C = part; q.ldc = p.N; q.out_f32 = 1; q.bias = nullptr; q.aux = nullptr; q.alpha = 1.0f;
     const int tiles = cdiv(p.M, 128) * cdiv(p.N, 128);
-    g_nt_last_kernel = EOE_NT_KERNEL_SPLIT_K;
-    { static bool once = (hipFuncSetAttribute((const void*)gemm_nt128_kernel<T, EOE_EPI_NONE, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem128_bytes(4)), true); (void)once; }
-    hipLaunchKernelGGL((gemm_nt128_kernel<T, EOE_EPI_NONE, 4>), dim3(tiles, S), dim3(256), smem128_bytes(4), s, q);
+    launch_gemm<gemm_nt128_kernel<T, EOE_EPI_NONE, 4>>(dim3(tiles, S), dim3(256), smem128_bytes(4), s, q);
     EOE_CHECK_LAUNCH("gemm_nt128 (split k)");
     hipLaunchKernelGGL((nt_splitk_finish_kernel<T>), dim3(cdiv(p.M * (p.N / 4), 256)), dim3(256), 0, s, (const float*)part, S, p.M, p.N, p.alpha,
                        p.bias, epi == EOE_EPI_RESIDUAL ? (const float*)p.aux : nullptr, p.ldaux, p.C, p.ldc, p.out_f32);
@@ -919,89 +865,102 @@ int launch_nt128_splitk(const GemmP& p, int epi, hipStream_t s) {
 
 int g_nt_flags = EOE_NT_DEFAULT_FLAGS;
 
+// persistent: one 8-wave workgroup per CU runs a strided sequence of the 256 x (32 NI) tiles
+template <int NI>
+int persistent_grid(const GemmP& p, int ncu) {
+    const int tiles = cdiv(p.M, BM) * cdiv(p.N, 32 * NI);
+    return tiles < ncu ? tiles : ncu;
+}
+
 template <typename T, int NI, int FLAGS>
-int launch_nt_f(const GemmP& p, int epi, int grid, hipStream_t s) {
-    g_nt_last_kernel = NI == 3 ? EOE_NT_KERNEL_PERSISTENT_256x96 : EOE_NT_KERNEL_PERSISTENT_256x128;
-#define EOE_NT_CASE(E)                                                                      \
-    case E:                                                                                 \
-        { static bool once = (hipFuncSetAttribute((const void*)gemm_nt_kernel<T, E, NI, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES), true); (void)once; } \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, E, NI, FLAGS>), dim3(grid), dim3(512), SMEM_BYTES, s, p); \
-        break;
-    switch (epi) {
-        EOE_NT_CASE(EOE_EPI_NONE)
-        EOE_NT_CASE(EOE_EPI_GELU)
-        EOE_NT_CASE(EOE_EPI_RESIDUAL)
-        EOE_NT_CASE(EOE_EPI_GELU_BWD)
-        default: return eoe_set_error(EOE_ERR_ARG, "gemm_nt: unknown epilogue %d", epi);
-    }
-#undef EOE_NT_CASE
+int launch_nt_f(const GemmP& p, int epi, int ncu, hipStream_t s) {
+    EOE_TRY(for_epilogue<EOE_ALL_EPILOGUES>(epi, [&](auto E) {
+        launch_gemm<gemm_nt_kernel<T, decltype(E)::value, NI, FLAGS>>(dim3(persistent_grid<NI>(p, ncu)), dim3(512), SMEM_BYTES, s, p);
+    }));
     EOE_CHECK_LAUNCH("gemm_nt");
     return finish_colsum(p, epi, 4, s);
 }
 
-// convolution variants (plain epilogue only): implicit patch matrix and / or the 256x64 tile for cout = 64
+// convolution variants (plain epilogue only): implicit patch matrix and / or the 256x64 tile for cout = 64 (NI = 2: no MFMA / LDS work on
+// columns that do not exist)
 template <typename T, int NI, int GATHER>
-int launch_nt_conv(const GemmP& p, int grid, hipStream_t s) {
-    static bool once = (hipFuncSetAttribute((const void*)gemm_nt_kernel<T, EOE_EPI_NONE, NI, EOE_NT_DEFAULT_FLAGS, GATHER>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES), true);
-    (void)once;
-    g_nt_last_kernel = GATHER ? EOE_NT_KERNEL_GATHER : EOE_NT_KERNEL_PERSISTENT_NARROW;
-    hipLaunchKernelGGL((gemm_nt_kernel<T, EOE_EPI_NONE, NI, EOE_NT_DEFAULT_FLAGS, GATHER>), dim3(grid), dim3(512), SMEM_BYTES, s, p);
+int launch_nt_conv(const GemmP& p, int ncu, hipStream_t s) {
+    launch_gemm<gemm_nt_kernel<T, EOE_EPI_NONE, NI, EOE_NT_DEFAULT_FLAGS, GATHER>>(dim3(persistent_grid<NI>(p, ncu)), dim3(512), SMEM_BYTES, s, p);
     EOE_CHECK_LAUNCH("gemm_nt");
     return finish_colsum(p, EOE_EPI_NONE, 4, s);
 }
 
 template <typename T, int NI>
-int launch_nt_ni(const GemmP& p, int epi, int grid, hipStream_t s) {
+int launch_nt_ni(const GemmP& p, int epi, int flags, int ncu, hipStream_t s) {
 #ifdef EOE_AB
-    switch (g_nt_flags & 3) {
-        case 0: return launch_nt_f<T, NI, 0>(p, epi, grid, s);
-        case 1: return launch_nt_f<T, NI, 1>(p, epi, grid, s);
-        case 2: return launch_nt_f<T, NI, 2>(p, epi, grid, s);
-        default: return launch_nt_f<T, NI, 3>(p, epi, grid, s);
+    switch (flags & 3) {
+        case 0: return launch_nt_f<T, NI, 0>(p, epi, ncu, s);
+        case 1: return launch_nt_f<T, NI, 1>(p, epi, ncu, s);
+        case 2: return launch_nt_f<T, NI, 2>(p, epi, ncu, s);
+        default: return launch_nt_f<T, NI, 3>(p, epi, ncu, s);
     }
 #else
-    return launch_nt_f<T, NI, EOE_NT_DEFAULT_FLAGS>(p, epi, grid, s);
+    return launch_nt_f<T, NI, EOE_NT_DEFAULT_FLAGS>(p, epi, ncu, s);
 #endif
 }
 
-template <typename T>
-int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
-    const int ncu = num_cus();
-    if (epi == EOE_EPI_NONE && p.N <= 64 && (gather == 0 || gather == 1 || gather == 2) && !(g_nt_flags & 64)) {
+// ------------------------------------------------------------------------------------------------ the route of a call
+// Which kernel an NT GEMM gets, and what its launch needs from the decision.  nt_route below is a pure function of its arguments: it calls
+// nothing of HIP, reads no global and launches nothing, so eoe_gemm_nt_route can ask it for any CU count on a machine without a GPU.
+struct NtRoute {
+    int kernel;              // EOE_NT_KERNEL_*
+    int mi = 0;              // rows per tile / 32 of the two-workgroup (4, 5) and one-wave (5, 8) kernels
+    int ni = 0;              // columns per tile / 32 of the persistent kernel (2, 3, 4)
+    int split_s = 0;         // EOE_NT_KERNEL_SPLIT_K: k-ranges per tile
+    int sk_rounds = -1;      // EOE_NT_KERNEL_EIGHT_WAVE_STREAM_K: data-parallel rounds in front of the stream-K part
+    // EOE_NT_KERNEL_GATHER covers three kernels: mi set = the two-workgroup kernel, ni set = the persistent one, neither = the 256 x 64 kernel
+};
+
+// 128- or 160-row tiles (MI = 4 or 5) for the two-workgroup kernel: whichever needs less (rounds over the 2 x #CU workgroup slots) x (rows per tile)
+int nt128_rows_mi(const GemmP& p, int ncu, bool tie_to_160) {
+    const int slots = 2 * ncu;
+    const long t4 = (long)cdiv(p.M, 128) * cdiv(p.N, 128), t5 = (long)cdiv(p.M, 160) * cdiv(p.N, 128);
+    const long c4 = (t4 + slots - 1) / slots * 128, c5 = (t5 + slots - 1) / slots * 160;
+    return (c5 < c4 || (tie_to_160 && c5 == c4)) ? 5 : 4;
+}
+
+// split k (launch_nt128_splitk; nt_flags bit 13 = 8192 switches it off): the k-ranges per tile S, or 0 where the split form does not apply (the
+// call then takes the plain launch).  The partial tiles must fit the slot area of the caller's workspace: 2 x #CUs slots of 256 x 256 floats
+int nt_split_s(const GemmP& p, int epi, int flags, int ncu) {
+    const int nk = p.K / BK;
+    if ((flags & 8192) || !p.split_k || p.M > 1024 || nk < 24 || (epi != EOE_EPI_NONE && epi != EOE_EPI_RESIDUAL) || p.colsum || p.colsum_sq || p.accumulate ||
+        (p.N & 15) || (p.ldc & 3) || (epi == EOE_EPI_RESIDUAL && (p.ldaux & 3)))
+        return 0;
+    int S = 8;
+    while (S > 1 && (nk % S) != 0) S >>= 1;
+    if (S < 2 || nk / S < 3) return 0;
+    if (!p.sk_part || (size_t)S * p.M * p.N > (size_t)2 * ncu * 65536) return 0;
+    return S;
+}
+
+// gather: 0, or the mode of the implicit patch matrix (eoe_gemm_nt: 3 = narrow-channel geometry); flags: the nt_flags option; ncu: the CU count
+NtRoute nt_route(const GemmP& p, int epi, int gather, int flags, int ncu) {
+    if (epi == EOE_EPI_NONE && p.N <= 64 && (gather == 0 || gather == 1 || gather == 2) && !(flags & 64)) {
         // cout <= 64: four 64x64 waves per 256x64 tile, two workgroups per CU (nt_flags bit 6: the persistent 256x64 kernel instead)
-        const int rc = gather == 2 ? launch_nt64<T, 2>(p, s) : (gather ? launch_nt64<T, 1>(p, s) : launch_nt64<T, 0>(p, s));
-        return rc ? rc : finish_colsum(p, EOE_EPI_NONE, 4, s);
+        return {gather ? EOE_NT_KERNEL_GATHER : EOE_NT_KERNEL_NARROW_256x64};
     }
-    if (gather == 1 && epi == EOE_EPI_NONE && p.N >= 128 && !(g_nt_flags & 2048)) {
+    if (gather == 1 && epi == EOE_EPI_NONE && p.N >= 128 && !(flags & 2048)) {
         // cout >= 128, one tap per k-tile: the two-workgroup kernel (nt_flags bit 11 = 2048: the persistent 256x128 kernel, A/B).  160-row
-        // tiles where they need fewer (rounds x rows) -- not with BatchNorm statistics in the epilogue, whose partial rows are per 64 rows
-        const int slots = 2 * ncu;
-        const long t4 = (long)cdiv(p.M, 128) * cdiv(p.N, 128), t5 = (long)cdiv(p.M, 160) * cdiv(p.N, 128);
-        const long c4 = (t4 + slots - 1) / slots * 128, c5 = (t5 + slots - 1) / slots * 160;
-        if (!p.colsum_sq && c5 < c4) return launch_nt128_gather<T, 5>(p, s);
-        return launch_nt128_gather<T, 4>(p, s);
+        // tiles where they need fewer (rounds x rows) -- strictly fewer: a tie stays with the 128-row tiles here -- and not with BatchNorm
+        // statistics in the epilogue, whose partial rows are per 64 rows
+        return {EOE_NT_KERNEL_GATHER, p.colsum_sq ? 4 : nt128_rows_mi(p, ncu, false)};
     }
-    if (gather || (epi == EOE_EPI_NONE && p.N <= 64)) {
-        const bool narrow = p.N <= 64;               // 256x64 tiles: no MFMA / LDS work on columns that do not exist
-        const int tiles = cdiv(p.M, BM) * cdiv(p.N, narrow ? 64 : 128);
-        const int grid = tiles < ncu ? tiles : ncu;
-        if (gather == 2) return narrow ? launch_nt_conv<T, 2, 2>(p, grid, s) : launch_nt_conv<T, 4, 2>(p, grid, s);
-        if (gather == 3) return narrow ? launch_nt_conv<T, 2, 3>(p, grid, s) : launch_nt_conv<T, 4, 3>(p, grid, s);
-        if (gather) return narrow ? launch_nt_conv<T, 2, 1>(p, grid, s) : launch_nt_conv<T, 4, 1>(p, grid, s);
-        return launch_nt_conv<T, 2, 0>(p, grid, s);
-    }
-    // Tile shape (tools/gemm_bench.py, M = 12800): the two-workgroup kernel (128- or 160-row tiles, launch_nt128_auto) wins on
+    if (gather || (epi == EOE_EPI_NONE && p.N <= 64))         // N <= 64: 256x64 tiles
+        return {gather ? EOE_NT_KERNEL_GATHER : EOE_NT_KERNEL_PERSISTENT_NARROW, 0, p.N <= 64 ? 2 : 4};
+    // Tile shape (tools/gemm_bench.py, M = 12800): the two-workgroup kernel (128- or 160-row tiles, nt128_rows_mi) wins on
     // every ViT shape -- most where the epilogue is heavy against a short K loop (GELU' x dY 116 -> 94 us, fp32 residual
     // 42 -> 32 us, GELU forward 107 -> 96 us once its epilogue math was cheap) and, with 160-row tiles, on the N = 768 shapes
     // whose 600 128x128 tiles need two rounds over the 512 workgroup slots (480 tiles of 160x128: one round; K = 3072:
     // 83 -> 68 us = 887 TF, K = 2304: 61 -> 50 us = 916 TF).  The persistent 256-row kernel keeps large square problems
     // (4096^3: 1046 vs 984 TF).  nt_flags: bit 3 forces the two-workgroup kernel, bit 2 forbids it, bit 4 / 5 force 128 / 160 rows.
     // the one-wave-per-SIMD kernel (gemm256.hip) has only the LDS-transposed epilogue compiled in
-    if ((g_nt_flags & (128 | 256)) && epilogue_direct_ok(p, epi)) {
-        g_nt_last_kernel = (g_nt_flags & 256) ? EOE_NT_KERNEL_ONE_WAVE_256x256 : EOE_NT_KERNEL_ONE_WAVE_160x256;
-        return eoe_launch_nt256(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, (g_nt_flags & 256) ? 8 : 5, s);
-    }
+    if ((flags & (128 | 256)) && epilogue_direct_ok(p, epi))
+        return (flags & 256) ? NtRoute{EOE_NT_KERNEL_ONE_WAVE_256x256, 8} : NtRoute{EOE_NT_KERNEL_ONE_WAVE_160x256, 5};
     const bool big = p.K >= 4096 && p.N >= 2048;
     // The one-wave-per-SIMD kernel (gemm256.hip; 160x256 or 256x256 tiles by the cost model below) for every large NT GEMM: OPT-IN
     // (nt_flags bit 9 = 512).  Stand-alone at M = 12800 (tools/gemm_bench.py, the same GEMM back to back, operands hot in the
@@ -1016,32 +975,28 @@ int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
     // layers): the one-wave kernel wins where the epilogue is the GELU pair of outputs behind a short K loop -- c_fc forward 1.167 against
     // 1.260 --, ties on the K >= 2304 shapes (-0.001 ... -0.010) and loses on QKV (+0.135), GELU' x dY (+0.057) and the two K = 768 -> 768
     // shapes (+0.056, +0.020).  So: c_fc forward only (nt_flags bit 10 = 1024 turns the rule off).
-    if (gather == 0 && p.split_k) {          // asked for: small M behind a long K (nt_flags bit 13 = 8192 switches it off)
-        const int rc = launch_nt128_splitk<T>(p, epi, s);
-        if (rc >= 0) return rc;
-    }
+    if (const int S = nt_split_s(p, epi, flags, ncu)) return {EOE_NT_KERNEL_SPLIT_K, 4, 0, S};       // asked for: small M behind a long K
     // the eight-wave 256 x 256 kernel (gemm_w8.hip; round 4) for the plain / GELU 16-bit shapes whose 256 x 256 tiles fill the CUs to >= 85 %
     // in every round (M = 12 800: N = 2304 -> 450 tiles = 2 rounds at 88 %: the in-projection, 55 against 65 us, same bits; N = 3072 -> 600
     // = 3 rounds at 78 %: stays on the 160 x 256 x 32 kernel below).  nt_flags bit 17 = 131072 switches it off, bit 18 = 262144 forces it
-    if (!(g_nt_flags & (131072 | 4 | 8 | 512)) && gather == 0 && p.M >= 2048 && eoe_w8_applies(&p, epi)) {
+    if (!(flags & (131072 | 4 | 8 | 512)) && p.M >= 2048 && eoe_w8_applies(&p, epi)) {
         const long tiles = (long)cdiv(p.M, 256) * (p.N / 256);
         // (round 5) opt-in, nt_flags bit 20 = 1048576: with the caller's stream-K workspace the fractional last round is cut along k over all
         // CUs (bit 21: the last full round joins the stream-K part; bit 22: stream-K part first).  Measured slower than the rules below on every
         // ViT shape (gemm_w8.hip, w8_sk_rounds)
-        if ((g_nt_flags & 262144) || eoe_w8_streamk(&p) || tiles * 100 >= ((tiles + ncu - 1) / ncu) * ncu * 85) {
-            g_nt_last_kernel = eoe_w8_streamk(&p) ? EOE_NT_KERNEL_EIGHT_WAVE_STREAM_K : EOE_NT_KERNEL_EIGHT_WAVE;
-            return eoe_launch_w8(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, s);
-        }
+        const int sk_rounds = eoe_w8_sk_rounds(&p, flags, ncu);
+        if (sk_rounds >= 0) return {EOE_NT_KERNEL_EIGHT_WAVE_STREAM_K, 0, 0, 0, sk_rounds};
+        if ((flags & 262144) || tiles * 100 >= ((tiles + ncu - 1) / ncu) * ncu * 85) return {EOE_NT_KERNEL_EIGHT_WAVE};
     }
     // the 160x256x32 two-workgroup kernel on the wide-N shapes (c_fc forward, GELU' x dY: 10.64 -> 10.54 ms per step, three interleaved
     // pairs, same bits; nt_flags bit 12 = 4096 switches it off)
-    if (!(g_nt_flags & (4096 | 4 | 8 | 512)) && gather == 0 && !p.colsum_sq && (p.N % 256) == 0 && p.N >= 2048 && (p.K % 32) == 0 && p.M >= 2048) {
+    if (!(flags & (4096 | 4 | 8 | 512)) && !p.colsum_sq && (p.N % 256) == 0 && p.N >= 2048 && (p.K % 32) == 0 && p.M >= 2048) {
         // only where its tiles fill the 2 x #CU workgroup slots to >= 90 % in every round (N = 3072 at M = 12 800: 960 of 1024; N = 2304: 720)
         const long tiles = (long)cdiv(p.M, 160) * (p.N / 256), slots = 2L * ncu;
-        if (tiles * 10 >= ((tiles + slots - 1) / slots) * slots * 9) return launch_nt128w<T>(p, epi, s);
+        if (tiles * 10 >= ((tiles + slots - 1) / slots) * slots * 9) return {EOE_NT_KERNEL_WIDE_160x256x32};
     }
-    const bool gelu_wide = epi == EOE_EPI_GELU && p.N >= 2048 && p.K <= 1024 && !(g_nt_flags & 1024);
-    if (((g_nt_flags & 512) || gelu_wide) && !(g_nt_flags & (4 | 8)) && epilogue_direct_ok(p, epi) && p.M >= 2048 && p.N >= 512) {
+    const bool gelu_wide = epi == EOE_EPI_GELU && p.N >= 2048 && p.K <= 1024 && !(flags & 1024);
+    if (((flags & 512) || gelu_wide) && !(flags & (4 | 8)) && epilogue_direct_ok(p, epi) && p.M >= 2048 && p.N >= 512) {
         // time of a launch in units of one 16-row x 256-column x 64-deep slab of MFMAs: rounds over the CUs x (rows per tile x
         // (k-tiles + 2 for the pipeline fill) + 30 for a tile's epilogue and hand-over)
         const int nk = p.K / BK;
@@ -1052,25 +1007,53 @@ int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
             const long cost = ((tiles + ncu - 1) / ncu) * ((long)mi * (nk + 2) + 30);
             if (!best || cost < best) { best = cost; mi_best = mi; }
         }
-        g_nt_last_kernel = mi_best == 8 ? EOE_NT_KERNEL_ONE_WAVE_256x256 : EOE_NT_KERNEL_ONE_WAVE_160x256;
-        return eoe_launch_nt256(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, mi_best, s);
+        return {mi_best == 8 ? EOE_NT_KERNEL_ONE_WAVE_256x256 : EOE_NT_KERNEL_ONE_WAVE_160x256, mi_best};
     }
-    if (big && !(g_nt_flags & (4 | 8)) && epilogue_direct_ok(p, epi) && p.M >= 2048) {
-        g_nt_last_kernel = EOE_NT_KERNEL_ONE_WAVE_256x256;
-        return eoe_launch_nt256(&p, std::is_same<T, f16_t>::value ? EOE_F16 : EOE_BF16, epi, 8, s);
+    if (big && !(flags & (4 | 8)) && epilogue_direct_ok(p, epi) && p.M >= 2048) return {EOE_NT_KERNEL_ONE_WAVE_256x256, 8};
+    if (!p.colsum_sq && ((flags & 8) || (!big && !(flags & 4)))) {
+        // (a tie goes to the 160-row tiles: N = 3072 at M = 12800 is 5 x 128 = 4 x 160 rounds x rows, and the in-step timing of
+        //  tools/nt_shapes_sweep.sh has GELU' x dY at 1.226 against 1.260 ms per step with them -- fewer, larger tiles per slot)
+        const bool five = (flags & 32) || (!(flags & 16) && nt128_rows_mi(p, ncu, true) == 5);
+        return five ? NtRoute{EOE_NT_KERNEL_TWO_WG_160, 5} : NtRoute{EOE_NT_KERNEL_TWO_WG_128, 4};
     }
-    if (!p.colsum_sq && ((g_nt_flags & 8) || (!big && !(g_nt_flags & 4)))) return launch_nt128_auto<T>(p, epi, s);
     // tile width: 256x128 unless 256x96 needs >= 10 % fewer (rounds x width) units over the CUs
     const int t4 = cdiv(p.M, BM) * cdiv(p.N, 128), t3 = cdiv(p.M, BM) * cdiv(p.N, 96);
     const int c4 = cdiv(t4, ncu) * 4, c3 = cdiv(t3, ncu) * 3;
-    const int force = (g_nt_flags >> 4) & 7;          // option bits 4-6: 0 = heuristic, 3 / 4 = force the tile width
+    const int force = (flags >> 4) & 7;               // option bits 4-6: 0 = heuristic, 3 / 4 = force the tile width
     const bool use3 = force ? (force == 3) : (c3 * 10 <= c4 * 9);
-    const int tiles = use3 ? t3 : t4;
-    const int grid = tiles < ncu ? tiles : ncu;      // persistent: one 8-wave workgroup per CU
-    return use3 ? launch_nt_ni<T, 3>(p, epi, grid, s) : launch_nt_ni<T, 4>(p, epi, grid, s);
+    return use3 ? NtRoute{EOE_NT_KERNEL_PERSISTENT_256x96, 0, 3} : NtRoute{EOE_NT_KERNEL_PERSISTENT_256x128, 0, 4};
 }
 
-int fill_params(const eoe_gemm_args* a, GemmP& p) {
+template <typename T>
+int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
+    const int flags = g_nt_flags, ncu = num_cus();
+    const NtRoute r = nt_route(p, epi, gather, flags, ncu);
+    g_nt_last_kernel = r.kernel;
+    switch (r.kernel) {
+        case EOE_NT_KERNEL_NARROW_256x64:
+        case EOE_NT_KERNEL_GATHER:
+            if (!r.mi && !r.ni) return gather == 2 ? launch_nt64<T, 2>(p, s) : (gather ? launch_nt64<T, 1>(p, s) : launch_nt64<T, 0>(p, s));
+            if (r.mi) return r.mi == 5 ? launch_nt128_gather<T, 5>(p, s) : launch_nt128_gather<T, 4>(p, s);
+            if (gather == 2) return r.ni == 2 ? launch_nt_conv<T, 2, 2>(p, ncu, s) : launch_nt_conv<T, 4, 2>(p, ncu, s);
+            if (gather == 3) return r.ni == 2 ? launch_nt_conv<T, 2, 3>(p, ncu, s) : launch_nt_conv<T, 4, 3>(p, ncu, s);
+            return r.ni == 2 ? launch_nt_conv<T, 2, 1>(p, ncu, s) : launch_nt_conv<T, 4, 1>(p, ncu, s);
+        case EOE_NT_KERNEL_PERSISTENT_NARROW: return launch_nt_conv<T, 2, 0>(p, ncu, s);
+        case EOE_NT_KERNEL_ONE_WAVE_160x256:
+        case EOE_NT_KERNEL_ONE_WAVE_256x256: return eoe_launch_nt256<T>(&p, epi, r.mi, s);
+        case EOE_NT_KERNEL_SPLIT_K: return launch_nt128_splitk<T>(p, epi, r.split_s, s);
+        case EOE_NT_KERNEL_EIGHT_WAVE:
+        case EOE_NT_KERNEL_EIGHT_WAVE_STREAM_K: return eoe_launch_w8<T>(&p, epi, r.sk_rounds, s);
+        case EOE_NT_KERNEL_WIDE_160x256x32: return launch_nt128w<T>(p, epi, s);
+        case EOE_NT_KERNEL_TWO_WG_160: return launch_nt128<T, 5>(p, epi, s);
+        case EOE_NT_KERNEL_TWO_WG_128: return launch_nt128<T, 4>(p, epi, s);
+        case EOE_NT_KERNEL_PERSISTENT_256x96: return launch_nt_ni<T, 3>(p, epi, flags, ncu, s);
+        default: return launch_nt_ni<T, 4>(p, epi, flags, ncu, s);
+    }
+}
+
+// Everything eoe_gemm_nt does before the launch that needs no GPU: the argument checks, the kernels' argument block for `ncu` CUs and the
+// gather mode.  Reads nothing behind the operand pointers.
+int fill_params(const eoe_gemm_args* a, int ncu, GemmP& p, int& mode) {
     EOE_CHECK_ARG(a != nullptr, "gemm: null args");
     EOE_CHECK_ARG(a->A && a->B && a->C, "gemm: null operand");
     EOE_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "gemm: bad shape %d %d %d", a->M, a->N, a->K);
@@ -1083,8 +1066,8 @@ int fill_params(const eoe_gemm_args* a, GemmP& p) {
     p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldaux = a->ldaux;
     p.out_f32 = a->out_f32; p.accumulate = a->accumulate; p.alpha = a->alpha; p.split_k = a->split_k;
     // the stream-K workspace (gemm_w8.hip): 8 KiB of ticket / flag words, then the partial-accumulator slots
-    p.sk_part = nullptr; p.sk_sync = nullptr; p.sk_rounds = 0; p.sk_flags = 0;
-    if (a->sk_workspace && a->sk_workspace_bytes >= (int64_t)EOE_NT_STREAMK_WORKSPACE_BYTES(num_cus()) && (((uintptr_t)a->sk_workspace) & 15) == 0) {
+    p.sk_part = nullptr; p.sk_sync = nullptr; p.sk_rounds = 0; p.sk_flags = (g_nt_flags & 4194304) ? 1 : 0;       // nt_flags bit 22: stream-K part first
+    if (a->sk_workspace && a->sk_workspace_bytes >= (int64_t)EOE_NT_STREAMK_WORKSPACE_BYTES(ncu) && (((uintptr_t)a->sk_workspace) & 15) == 0) {
         p.sk_sync = (int*)a->sk_workspace;
         p.sk_part = (float*)((char*)a->sk_workspace + 8192);
     }
@@ -1131,37 +1114,10 @@ int fill_params(const eoe_gemm_args* a, GemmP& p) {
     if (dbg & 1) { p.bytesA = 0; p.bytesB = 0; }
     p.dbg = dbg | ((g_nt_flags & 524288) ? 32 : 0) | ((g_nt_flags & 8388608) ? 64 : 0);       // nt_flags bit 19: xcd_halves off; bit 23: nt128w's old LDS image (A/B)
     p.stamp = nullptr;
-    static const int stampon = getenv("EOE_GEMM_STAMP") ? atoi(getenv("EOE_GEMM_STAMP")) : 0;
-    if (stampon) {
-        static unsigned long long* buf = [] { void* b = nullptr; (void)hipMalloc(&b, 4096 * 16 * 8); return (unsigned long long*)b; }();
-        (void)hipMemsetAsync(buf, 0, 4096 * 16 * 8, 0);
-        p.stamp = buf;
-        g_stamp_buf = buf;
-    }
     if (a->epilogue == EOE_EPI_GELU) EOE_CHECK_ARG(!a->out_f32, "gemm: the GELU epilogue needs a 16-bit C");      // aux_out optional
     if (a->epilogue == EOE_EPI_RESIDUAL) EOE_CHECK_ARG(a->aux && a->out_f32, "gemm: RESIDUAL epilogue needs aux, fp32 C");
     if (a->epilogue == EOE_EPI_GELU_BWD) EOE_CHECK_ARG(a->aux, "gemm: GELU_BWD epilogue needs aux");
-    return 0;
-}
-
-}  // namespace
-
-int eoe_nt_flags() { return g_nt_flags; }          // for gemm_w8.hip's launcher
-
-extern "C" int eoe_gemm_nt(const eoe_gemm_args* a, void* stream) {
-    GemmP p;
-    EOE_TRY(fill_params(a, p));
-    const int osz = a->out_f32 ? 4 : 2;
-    // diagnostics (EOE_PROF_SHAPES=1): one profile row per (shape, epilogue) instead of one for all NT GEMMs
-    static const bool by_shape = getenv("EOE_PROF_SHAPES") != nullptr;
-    char pname[32] = "gemm_nt";
-    if (by_shape) snprintf(pname, sizeof(pname), "nt_%dx%dx%d_e%d%s", a->M, a->N, a->K, a->epilogue, a->colsum ? "c" : "");
-    ProfScope ps(pname, 2.0 * a->M * a->N * a->K,
-                 2.0 * ((a->gather ? (double)a->geo.n * a->geo.H * a->geo.W * a->geo.C : (double)a->M * a->K) + (double)a->N * a->K) +
-                     (double)osz * a->M * a->N *
-                     (a->epilogue == EOE_EPI_GELU ? 2 : 1) + (a->epilogue == EOE_EPI_RESIDUAL ? 4.0 * a->M * a->N : 0.0) +
-                     (a->epilogue == EOE_EPI_GELU_BWD ? 2.0 * a->M * a->N : 0.0), stream);
-    const int mode = (a->gather == 1 && p.gkh) ? 3 : a->gather;      // narrow-channel geometry -> per-piece tap decoding
+    mode = (a->gather == 1 && p.gkh) ? 3 : a->gather;      // narrow-channel geometry -> per-piece tap decoding
     // fused column sums: through partial rows in the workspace (one row per 64 / 80 output rows) when it is large enough
     if (a->colsum && a->workspace && a->workspace_bytes >= (int64_t)EOE_NT_COLSUM_WORKSPACE_BYTES(a->M, a->N))
         p.colsum_part = (float*)a->workspace, p.colsum_blocked = ((a->N & 63) == 0 && (a->N & 3) == 0) ? 1 : 0;
@@ -1176,10 +1132,52 @@ extern "C" int eoe_gemm_nt(const eoe_gemm_args* a, void* stream) {
         p.colsum_sq = 1;
         p.colsum_blocked = 0;
     }
+    return 0;
+}
+
+// diagnostics (EOE_GEMM_STAMP=1): the buffer of the per-workgroup s_memtime stamps, zeroed in front of every launch
+void attach_stamps(GemmP& p) {
+    static const int stampon = getenv("EOE_GEMM_STAMP") ? atoi(getenv("EOE_GEMM_STAMP")) : 0;
+    if (stampon) {
+        static unsigned long long* buf = [] { void* b = nullptr; (void)hipMalloc(&b, 4096 * 16 * 8); return (unsigned long long*)b; }();
+        (void)hipMemsetAsync(buf, 0, 4096 * 16 * 8, 0);
+        p.stamp = buf;
+        g_stamp_buf = buf;
+    }
+}
+
+}  // namespace
+
+extern "C" int eoe_gemm_nt(const eoe_gemm_args* a, void* stream) {
+    GemmP p;
+    int mode;
+    EOE_TRY(fill_params(a, num_cus(), p, mode));
+    attach_stamps(p);
+    const int osz = a->out_f32 ? 4 : 2;
+    // diagnostics (EOE_PROF_SHAPES=1): one profile row per (shape, epilogue) instead of one for all NT GEMMs
+    static const bool by_shape = getenv("EOE_PROF_SHAPES") != nullptr;
+    char pname[32] = "gemm_nt";
+    if (by_shape) snprintf(pname, sizeof(pname), "nt_%dx%dx%d_e%d%s", a->M, a->N, a->K, a->epilogue, a->colsum ? "c" : "");
+    ProfScope ps(pname, 2.0 * a->M * a->N * a->K,
+                 2.0 * ((a->gather ? (double)a->geo.n * a->geo.H * a->geo.W * a->geo.C : (double)a->M * a->K) + (double)a->N * a->K) +
+                     (double)osz * a->M * a->N *
+                     (a->epilogue == EOE_EPI_GELU ? 2 : 1) + (a->epilogue == EOE_EPI_RESIDUAL ? 4.0 * a->M * a->N : 0.0) +
+                     (a->epilogue == EOE_EPI_GELU_BWD ? 2.0 * a->M * a->N : 0.0), stream);
     return a->dtype == EOE_F16 ? launch_nt<f16_t>(p, a->epilogue, mode, (hipStream_t)stream)
                                : launch_nt<bf16_t>(p, a->epilogue, mode, (hipStream_t)stream);
 }
 
+// the route eoe_gemm_nt would take with these arguments on `ncu` CUs (<= 0: the current device's), without launching: EOE_NT_KERNEL_* in
+// *kernel.  With ncu > 0 it calls nothing of HIP and reads nothing behind the operand pointers
+extern "C" int eoe_gemm_nt_route(const eoe_gemm_args* a, int ncu, int* kernel) {
+    EOE_CHECK_ARG(kernel != nullptr, "eoe_gemm_nt_route: null pointer");
+    if (ncu <= 0) ncu = num_cus();
+    GemmP p;
+    int mode;
+    EOE_TRY(fill_params(a, ncu, p, mode));
+    *kernel = nt_route(p, a->epilogue, mode, g_nt_flags, ncu).kernel;
+    return 0;
+}
 
 // diagnostics: copies the per-workgroup s_memtime stamps of the last gemm_nt launch (EOE_GEMM_STAMP=1) to the host
 extern "C" int eoe_debug_gemm_stamps(unsigned long long* out, int n_words) {

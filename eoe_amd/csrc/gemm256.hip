@@ -314,38 +314,29 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_kernel(GemmP p) {
 }
 
 
-extern int g_nt_flags;
-
 template <typename T, int MI>
 int launch_nt256(const GemmP& p, int epi, hipStream_t s) {
     const int tiles = cdiv(p.M, 32 * MI) * cdiv(p.N, 256);
     const int ncu = num_cus();
     const int grid = tiles < ncu ? tiles : ncu;
-#define EOE_NT256_CASE(E)                                                                   \
-    case E:                                                                                 \
-        { static bool once = (hipFuncSetAttribute((const void*)gemm_nt256_kernel<T, E, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem256_bytes(MI)), true); (void)once; } \
-        hipLaunchKernelGGL((gemm_nt256_kernel<T, E, MI>), dim3(grid), dim3(256), smem256_bytes(MI), s, p); \
-        break;
-    switch (epi) {
-        EOE_NT256_CASE(EOE_EPI_NONE)
-        EOE_NT256_CASE(EOE_EPI_GELU)
-        EOE_NT256_CASE(EOE_EPI_RESIDUAL)
-        EOE_NT256_CASE(EOE_EPI_GELU_BWD)
-        default: return eoe_set_error(EOE_ERR_ARG, "gemm_nt: unknown epilogue %d", epi);
-    }
-#undef EOE_NT256_CASE
+    EOE_TRY(for_epilogue<EOE_ALL_EPILOGUES>(epi, [&](auto E) {
+        launch_gemm<gemm_nt256_kernel<T, decltype(E)::value, MI>>(dim3(grid), dim3(256), smem256_bytes(MI), s, p);
+    }));
     EOE_CHECK_LAUNCH("gemm_nt256");
     return finish_colsum(p, epi, MI, s);
 }
 
 }  // namespace
 
-int eoe_launch_nt256(const void* gemm_p, int dtype, int epi, int mi, hipStream_t s) {
+// for gemm.hip's launcher (which sees GemmP as its own type: the struct lives in an unnamed namespace)
+template <typename T>
+int eoe_launch_nt256(const void* gemm_p, int epi, int mi, hipStream_t s) {
     const GemmP& p = *(const GemmP*)gemm_p;
 #ifdef EOE_DEV256          // development builds: one instantiation family only (compile time)
     return launch_nt256<f16_t, 5>(p, epi, s);
 #else
-    if (dtype == EOE_F16) return mi == 8 ? launch_nt256<f16_t, 8>(p, epi, s) : launch_nt256<f16_t, 5>(p, epi, s);
-    return mi == 8 ? launch_nt256<bf16_t, 8>(p, epi, s) : launch_nt256<bf16_t, 5>(p, epi, s);
+    return mi == 8 ? launch_nt256<T, 8>(p, epi, s) : launch_nt256<T, 5>(p, epi, s);
 #endif
 }
+template int eoe_launch_nt256<f16_t>(const void*, int, int, hipStream_t);
+template int eoe_launch_nt256<bf16_t>(const void*, int, int, hipStream_t);

@@ -1,6 +1,7 @@
 // Shared pieces of the NT GEMM kernels (gemm.hip, gemm256.hip): the kernel argument block, the two epilogues and the waits.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -524,6 +525,22 @@ static inline int num_cus() {
     static const int ncu = [] { int d = 0, n = 256; hipDeviceProp_t pr; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) n = pr.multiProcessorCount; return n; }();
     return ncu;
 }
+
+// The launch every NT launcher makes: KERNEL(p), whose first launch raises the kernel's dynamic-LDS limit to what its ring needs.
+template <auto KERNEL>
+static void launch_gemm(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const GemmP& p) {
+    static bool once = (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), true);
+    (void)once;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, s, p);
+}
+
+// f(E) with the epilogue code as a compile-time constant (decltype(E)::value), for the epilogues EPIS a kernel is built with
+template <int... EPIS, typename F>
+static int for_epilogue(int epi, F&& f) {
+    const bool built = (... || (epi == EPIS && (f(std::integral_constant<int, EPIS>{}), true)));
+    return built ? 0 : eoe_set_error(EOE_ERR_ARG, "gemm_nt: unknown epilogue %d", epi);
+}
+#define EOE_ALL_EPILOGUES EOE_EPI_NONE, EOE_EPI_GELU, EOE_EPI_RESIDUAL, EOE_EPI_GELU_BWD
 
 static int finish_colsum(const GemmP& p, int epi, int mi, hipStream_t s) {
     if (!p.colsum_part || !p.colsum || p.colsum_sq || epi == EOE_EPI_GELU) return 0;

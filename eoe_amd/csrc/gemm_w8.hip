@@ -14,9 +14,6 @@
 // k-tiles in flight under it.  The tile's bias row reaches LDS by one extra piece of wave 0 (two alternating slots).
 // Same products in the same k order as every other NT kernel, same epilogue arithmetic: bitwise the same results.
 #include "gemm_common.h"
-#include <type_traits>
-
-int eoe_nt_flags();             // gemm.hip: the nt_flags option
 
 namespace {
 
@@ -464,44 +461,31 @@ __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(GemmP p) {
 // (with nt_flags bit 21: the last full round too -- "two-tile" stream-K) is cut along k over all workgroups, XCD by XCD.  Preconditions: the
 // caller's workspace, one workgroup per CU on a multiple of 8 CUs, >= 4 k-tiles per tile, and every XCD's share >= 4 k-tiles per workgroup
 // (segments are then >= 2 k-tiles long, which the kernel's pipeline needs)
-int w8_sk_rounds(const GemmP& p, int tiles, int ncu) {
-    const int g_nt_flags = eoe_nt_flags();
-    if (!(g_nt_flags & 1048576) || !p.sk_part || !p.sk_sync || (ncu & 7) || ncu > 256 || tiles <= 0) return -1;
+// flags: the nt_flags option
+int w8_sk_rounds(const GemmP& p, int tiles, int flags, int ncu) {
+    if (!(flags & 1048576) || !p.sk_part || !p.sk_sync || (ncu & 7) || ncu > 256 || tiles <= 0) return -1;
     const int nk = p.K / BK;
     if (nk < 4 || tiles % ncu == 0) return -1;
     int R = tiles / ncu;
-    if ((g_nt_flags & 2097152) && R >= 1) R -= 1;
+    if ((flags & 2097152) && R >= 1) R -= 1;
     const int tsk = tiles - R * ncu;
     if (tsk < 8 || (long)(tsk / 8) * nk < 4L * (ncu / 8)) return -1;
     return R;
 }
 
+// sk_rounds: w8_sk_rounds' plan of this launch
 template <typename T>
-int launch_w8(const GemmP& p0, int epi, hipStream_t s) {
+int launch_w8(const GemmP& p0, int epi, int sk_rounds, hipStream_t s) {
     GemmP p = p0;
     const int tiles = cdiv(p.M, 256) * (p.N / 256);
     const int ncu = num_cus();
-    const int R = w8_sk_rounds(p, tiles, ncu);
-    const bool sk = R >= 0;
-    const int grid = sk ? ncu : (tiles < ncu ? tiles : ncu);
-    p.sk_rounds = sk ? R : 0;
-    p.sk_flags = (eoe_nt_flags() & 4194304) ? 1 : 0;
-#define EOE_W8_LAUNCH(E, SK_)                                                               \
-    do {                                                                                    \
-        static bool once = (hipFuncSetAttribute((const void*)gemm_w8_kernel<T, E, SK_>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_SMEM_BYTES), true); (void)once; \
-        hipLaunchKernelGGL((gemm_w8_kernel<T, E, SK_>), dim3(grid), dim3(512), W8_SMEM_BYTES, s, p); \
-    } while (0)
-#define EOE_W8_CASE(E)                                                                      \
-    case E:                                                                                 \
-        if (sk) EOE_W8_LAUNCH(E, true); else EOE_W8_LAUNCH(E, false);                       \
-        break;
-    switch (epi) {
-        EOE_W8_CASE(EOE_EPI_NONE)
-        EOE_W8_CASE(EOE_EPI_GELU)
-        default: return eoe_set_error(EOE_ERR_ARG, "gemm_w8: epilogue %d is not built", epi);
-    }
-#undef EOE_W8_CASE
-#undef EOE_W8_LAUNCH
+    const bool sk = sk_rounds >= 0;
+    const dim3 grid(sk ? ncu : (tiles < ncu ? tiles : ncu));
+    p.sk_rounds = sk ? sk_rounds : 0;
+    EOE_TRY((for_epilogue<EOE_EPI_NONE, EOE_EPI_GELU>(epi, [&](auto E) {
+        if (sk) launch_gemm<gemm_w8_kernel<T, decltype(E)::value, true>>(grid, dim3(512), W8_SMEM_BYTES, s, p);
+        else launch_gemm<gemm_w8_kernel<T, decltype(E)::value, false>>(grid, dim3(512), W8_SMEM_BYTES, s, p);
+    })));
     EOE_CHECK_LAUNCH("gemm_w8");
     return 0;
 }
@@ -520,17 +504,20 @@ bool eoe_w8_applies(const void* gemm_p, int epi) {
     return c_bytes < 0x7fffffffull && a_reach < 0x7fffffffull;
 }
 
-// would the launch run in the stream-K form (the dispatcher's rule in gemm.hip asks)
-bool eoe_w8_streamk(const void* gemm_p) {
+// the stream-K plan of the launch, -1 for the data-parallel form (nt_route in gemm.hip asks)
+int eoe_w8_sk_rounds(const void* gemm_p, int flags, int ncu) {
     const GemmP& p = *(const GemmP*)gemm_p;
-    return w8_sk_rounds(p, cdiv(p.M, 256) * (p.N / 256), num_cus()) >= 0;
+    return w8_sk_rounds(p, cdiv(p.M, 256) * (p.N / 256), flags, ncu);
 }
 
-int eoe_launch_w8(const void* gemm_p, int dtype, int epi, hipStream_t s) {
+template <typename T>
+int eoe_launch_w8(const void* gemm_p, int epi, int sk_rounds, hipStream_t s) {
     const GemmP& p = *(const GemmP*)gemm_p;
 #ifdef EOE_W8_DEV          // development builds: one instantiation family only (compile time)
-    return launch_w8<f16_t>(p, epi, s);
+    return launch_w8<f16_t>(p, epi, sk_rounds, s);
 #else
-    return dtype == EOE_F16 ? launch_w8<f16_t>(p, epi, s) : launch_w8<bf16_t>(p, epi, s);
+    return launch_w8<T>(p, epi, sk_rounds, s);
 #endif
 }
+template int eoe_launch_w8<f16_t>(const void*, int, int, hipStream_t);
+template int eoe_launch_w8<bf16_t>(const void*, int, int, hipStream_t);

@@ -1042,6 +1042,10 @@ enum {
     EOE_NT_KERNEL_SPLIT_K = 12,              /* gemm.hip: split k (eoe_gemm_args.split_k) + the in-order finish kernel */
     EOE_NT_KERNEL_GATHER = 13                /* any implicit-convolution (gather != 0) form */
 };
+/* The route eoe_gemm_nt would take with these arguments and the current "nt_flags" on a device of `ncu` CUs (ncu <= 0: the current device's
+ * count), in *kernel; nothing is launched and "nt_last_kernel" stays.  The same argument checks as eoe_gemm_nt.  With ncu > 0 the call touches
+ * no GPU and reads nothing behind the operand pointers: any non-null, 16-byte aligned addresses will do, on a machine without a GPU too. */
+int eoe_gemm_nt_route(const eoe_gemm_args* args, int ncu, int* kernel);
 /* diagnostics only (EOE_GEMM_STAMP=1): in-kernel s_memtime stamps of the last eoe_gemm_nt launch, 16 words per workgroup */
 int eoe_debug_gemm_stamps(unsigned long long* out, int n_words);
 int eoe_prof_collect(eoe_prof_entry* out, int max_entries, int* n_out);

@@ -52,8 +52,9 @@ per K, then overall), so that no kind or K is tied to one N and every kind meets
 GENERIC_KINDS runs once through `epilogue_generic` on the two-workgroup, persistent and 160 x 256 x 32 routes, forced in turn by
 N % 16 != 0 (not at N = 2048), by ldc % 8 != 0 and by a C pointer 8 bytes off; the GELU pair with each forcing.  Routes whose reach depends
 on the CU count (the 160 x 256 x 32 kernel; the eight-wave kernel's fall-backs choose 128- or 160-row tiles by it) get M and the expected
-code from `dispatch(case, ncu)`, a Python restatement of launch_nt's conditions that only builds tables: the GPU tests assert
-`nt_last_kernel` against the real dispatcher.
+code from `dispatch(case, ncu)`, a Python restatement of nt_route's conditions (gemm.hip) that only builds tables: the CPU tests hold it
+against the real rule, asked through eoe_gemm_nt_route, on every row at 64 to 304 CUs, and the GPU tests assert that the route asked for is
+the route that ran (`nt_last_kernel`).
 The wide-tile and stream-K TN forms need workload-sized groups (216 tiles of 256 x 128 on 256 CUs) and keep their present tests
 (test_gemm_tn_wide_tiles, test_gemm_tn_grouped_stream_k); nothing here shrinks them.
 
@@ -181,7 +182,7 @@ def _cdiv(a, b):
 
 
 def dispatch(c, ncu=DEFAULT_CUS):
-    """launch_nt of gemm.hip for gather == 0 without the opt-in stream-K bits: the name of the route"""
+    """nt_route of gemm.hip for gather == 0 without the opt-in stream-K bits: the name of the route"""
     f, k = c["flags"], kind_of(c)
     M, N, K = c["M"], c["N"], c["K"]
     if k["epi"] == "none" and N <= 64:
@@ -671,6 +672,61 @@ def nt_memory(c, dtype):
     if k["bias"]:
         m["bias"] = embed(x["bias"][None], N, "nan")
     return m
+
+
+# ------------------------------------------------------------------------------------------------ the arguments of the C call
+def sk_workspace_bytes(ncu):
+    """EOE_NT_STREAMK_WORKSPACE_BYTES of include/eoe_hip.h"""
+    return 8192 + ncu * 2 * 256 * 256 * 4
+
+
+def nt_args(c, dtype, addr, sk_bytes):
+    """the eoe_gemm_args of case c, filled as ops.gemm_nt fills them, for eoe_gemm_nt and eoe_gemm_nt_route alike.  addr: name -> address of
+    the first element of 'a', 'b', 'C' and of what the kind has of 'bias', 'aux', 'aux_out', 'colsum', and of the workspaces 'colsum_ws' (the
+    partial rows of a kind with column sums "ws"), 'colstats_ws' and 'sk_ws' (sk_bytes long; attached where ops.gemm_nt attaches it: with
+    split_k, or at M >= 2048 and N % 256 == 0)"""
+    from eoe_amd import _lib
+    k, M, N = kind_of(c), c["M"], c["N"]
+    has = lambda n, on: addr[n] if on else None               # noqa: E731
+    g = _lib.GemmArgs(addr["a"], addr["b"], addr["C"], has("bias", k["bias"]), has("aux", k["epi"] in ("residual", "gelu_bwd")),
+                      has("aux_out", k["aux_out"]), has("colsum", k["colsum"]), M, N, c["K"], c["lda"], c["ldb"], c["ldc"], c["ldaux"],
+                      {torch.float16: _lib.EOE_F16, torch.bfloat16: _lib.EOE_BF16}[dtype], EPI_CODE[k["epi"]],
+                      0 if k["out"] == "16" else 1, 1 if k["accumulate"] else 0, float(k["alpha"]))
+    part_bytes = _cdiv(M, 64) * N * 4                           # EOE_NT_COLSUM_WORKSPACE_BYTES
+    if k["colsum"] == "ws":
+        g.workspace, g.workspace_bytes = addr["colsum_ws"], part_bytes
+    if k["colstats"]:
+        g.workspace, g.workspace_bytes, g.colstats = addr["colstats_ws"], 2 * part_bytes, 1
+    g.split_k = 1 if c["split_k"] else 0
+    if c["split_k"] or (M >= 2048 and N % 256 == 0):
+        g.sk_workspace, g.sk_workspace_bytes = addr["sk_ws"], sk_bytes
+    return g
+
+
+def nt_starts(c, dtype):
+    """name -> (first element, element size) of every view nt_memory lays out for case c, without building the buffers"""
+    k = kind_of(c)
+    M, N, K = c["M"], c["N"], c["K"]
+    osz = 2 if k["out"] == "16" else 4
+    coff = c["c_off_bytes"] // osz
+    s = {"a": (layout(M, K, c["lda"])[1], 2), "b": (layout(N, K, c["ldb"])[1], 2), "C": (layout(M, N, c["ldc"], coff)[1], osz)}
+    if k["epi"] in ("residual", "gelu_bwd"):
+        s["aux"] = (layout(M, N, c["ldaux"])[1], 4 if k["epi"] == "residual" else 2)
+    if k["aux_out"]:
+        s["aux_out"] = (layout(M, N, c["ldc"], coff)[1], 2)
+    if k["colsum"]:
+        s["colsum"] = (layout(1, N, N)[1], 4)
+    if k["bias"]:
+        s["bias"] = (layout(1, N, N)[1], 4)
+    return s
+
+
+def fake_addresses(c, dtype, sk_off=0):
+    """addresses for eoe_gemm_nt_route, which reads nothing behind them: every buffer of nt_memory at a 256-byte aligned base of its own, its
+    view where nt_starts has it (so C is as far off 16 bytes as on the GPU); the workspaces aligned, the stream-K one sk_off bytes off"""
+    addr = {n: (i + 1) << 32 | start * es for i, (n, (start, es)) in enumerate(sorted(nt_starts(c, dtype).items()))}
+    addr.update(colsum_ws=20 << 32, colstats_ws=21 << 32, sk_ws=(22 << 32) + sk_off)
+    return addr
 
 
 def restate32(c, dtype, mem, mutant=None):

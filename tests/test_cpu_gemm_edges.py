@@ -157,6 +157,81 @@ def test_wide_route_rows_follow_the_cu_count():
         assert all(c["expect"] == "wide_160x256x32" for c in u.nt_table(ncu)["wide_160x256x32"])
 
 
+def _route(args, ncu, flags):
+    """the name of the route eoe_gemm_nt_route gives under nt_flags = flags (restored afterwards)"""
+    from eoe_amd import _lib
+    old = _lib.set_option("nt_flags", flags)
+    try:
+        return u.NT_KERNELS[_lib.gemm_nt_route(args, ncu)]
+    finally:
+        _lib.set_option("nt_flags", old)
+
+
+@pytest.mark.parametrize("ncu", (64, 104, 228, 256, 304))
+def test_route_query_gives_the_tables_route_on_every_cu_count(ncu):
+    """the product's rule (nt_route of gemm.hip, asked through eoe_gemm_nt_route: no GPU, nothing launched) against gemm_util.dispatch on
+    every row of the tables, with the arguments the GPU test launches with"""
+    bad = {}
+    for cases in u.nt_table(ncu).values():
+        for c in cases:
+            for dt in u.DTYPES:
+                got = _route(u.nt_args(c, dt, u.fake_addresses(c, dt), u.sk_workspace_bytes(ncu)), ncu, c["flags"])
+                if got != c["expect"]:
+                    bad[f"{c['id']}-{u.DTNAME[dt]}"] = (got, c["expect"])
+    assert not bad, f"{len(bad)} rows: {bad}"
+
+
+def test_fake_addresses_lie_where_the_gpu_tests_views_lie():
+    for route in ("two_wg_128", "persistent_256x96", "narrow_256x64", "one_wave_160x256"):
+        for c in u.nt_table()[route]:
+            for dt in u.DTYPES:
+                mem, st = u.nt_memory(c, dt), u.nt_starts(c, dt)
+                assert {n: (start, flat.element_size()) for n, (flat, start) in mem.items()} == st, c["id"]
+                assert all(a % 16 == (st[n][0] * st[n][1]) % 16 for n, a in u.fake_addresses(c, dt).items() if n in st)
+
+
+def test_route_query_stream_k_needs_a_usable_workspace():
+    """test_gpu_round5.test_streamk_and_splitk_fall_back_without_a_usable_workspace's shape, eight-wave kernel forced, stream-K asked for, on
+    256 CUs: the stream-K form only with a whole, aligned workspace"""
+    c = u.nt_case("eight_wave", "none_16", 4096, 2304, 768, flags=1 | 262144 | 1048576)
+    full = u.sk_workspace_bytes(256)
+
+    def route(sk_ws, nbytes):
+        return _route(u.nt_args(c, torch.float16, dict(u.fake_addresses(c, torch.float16), sk_ws=sk_ws), nbytes), 256, c["flags"])
+
+    ws = u.fake_addresses(c, torch.float16)["sk_ws"]
+    assert ws % 16 == 0 and route(ws, full) == "eight_wave_stream_k"
+    assert route(None, 0) == "eight_wave" and route(ws, full - 1) == "eight_wave" and route(ws + 8, full) == "eight_wave"
+
+
+@pytest.mark.parametrize("mode", ("one_tap_per_k_tile", "packed_first_layer", "narrow_channels"))
+def test_route_query_gather_forms(mode):
+    """one implicit-convolution call per gather mode (1, 2, and 1 with 8 channels, which eoe_gemm_nt decodes as mode 3) at the smallest
+    geometry the argument checks accept: one output pixel of one image, one 64-deep k-tile"""
+    from eoe_amd import _lib
+    C_, W, stride, gather = {"one_tap_per_k_tile": (64, 1, 1, 1), "packed_first_layer": (4, 8, 2, 2), "narrow_channels": (8, 1, 1, 1)}[mode]
+    c = u.nt_case("narrow_256x64", "none_f32", 1, 8, 64)
+    g = u.nt_args(c, torch.bfloat16, u.fake_addresses(c, torch.bfloat16), 0)
+    g.gather, g.geo = gather, _lib.ConvGeometry(n=1, H=1, W=W, C=C_, kh=1, kw=1, stride=stride, pad=0, Ho=1, Wo=1)
+    for ncu in (64, 256):
+        assert _route(g, ncu, 1) == "gather"
+
+
+def test_route_query_flag_64_sends_narrow_n_to_the_persistent_kernel():
+    c = u.nt_case("persistent_narrow", "none_f32", 257, 48, 64, flags=1 | 64)
+    g = u.nt_args(c, torch.bfloat16, u.fake_addresses(c, torch.bfloat16), 0)
+    assert _route(g, 256, 1 | 64) == "persistent_narrow" and _route(g, 256, 1) == "narrow_256x64"
+
+
+def test_route_query_checks_its_arguments_like_the_launch():
+    from eoe_amd import _lib
+    c = u.nt_case("two_wg_128", "none_f32", 65, 72, 64)
+    g = u.nt_args(c, torch.bfloat16, u.fake_addresses(c, torch.bfloat16), 0)
+    g.K = 65
+    with pytest.raises(_lib.EoeError, match="multiple of 64"):
+        _lib.gemm_nt_route(g, 256)
+
+
 def test_inputs_are_16_bit_values_and_pure_functions_of_their_name():
     c = u.nt_table()["two_wg_128"][3]
     for dt in u.DTYPES:

@@ -4,8 +4,8 @@ against the fp64 contract of tests/gemm_util.py (its docstring has the tables, t
 Every output (C, aux_out, colsum) lies in a flat buffer with PAD_ROWS canary rows in front of and behind it and canary columns in every
 stride gap (fp32: a NaN-free sentinel, so that an add shows; 16 bit: a fixed bit pattern), checked bitwise after each launch; the gaps and
 pad rows of every input hold NaN, so that a read at the wrong stride or past M or N poisons the result.  Every NT case asserts the route
-the dispatcher took (`nt_last_kernel`): a case that falls through to another kernel fails.  Cases of M >= 2048 are compared with fp64 on the
-first and last 8 rows of every row-tile boundary plus 240 seeded rows, and over the whole tensor bitwise with the two-workgroup 160-row
+the dispatcher took (`nt_last_kernel`), and that eoe_gemm_nt_route named it beforehand: a case that falls through to another kernel
+fails.  Cases of M >= 2048 are compared with fp64 on the first and last 8 rows of every row-tile boundary plus 240 seeded rows, and over the whole tensor bitwise with the two-workgroup 160-row
 kernel where test_gpu_ops.test_gemm_nt_eight_wave / test_gemm_nt_wide_kernel_tile_order_and_image establish that equality."""
 import ctypes as C
 
@@ -37,40 +37,37 @@ def _dev(mem):
     return {n: (flat.cuda(), start) for n, (flat, start) in mem.items()}
 
 
-def _view(d, name, rows, cols, ld):
-    flat, start = d[name]
-    return flat.as_strided((rows, cols), (ld, 1), start)
-
-
 def _launch_nt(ops, c, dtype, mem, flags):
-    """one launch of case c on the flat buffers `mem` (CPU; they come back with the results): (route code, {'stats'})"""
+    """one launch of case c on the flat buffers `mem` (CPU; they come back with the results), with the arguments of gemm_util.nt_args:
+    (route code, {'stats'}).  The route eoe_gemm_nt_route names for these arguments before the launch must be the one that ran"""
     from eoe_amd import _lib
-    k, M, N, K = u.kind_of(c), c["M"], c["N"], c["K"]
+    k, M, N = u.kind_of(c), c["M"], c["N"]
     d = _dev(mem)
-    kw, extra = {}, {}
-    if k["bias"]:
-        kw["bias"] = _view(d, "bias", 1, N, N)[0]
-    if "aux" in d:
-        kw["aux"] = _view(d, "aux", M, N, c["ldaux"])
-    if k["aux_out"]:
-        kw["aux_out"] = _view(d, "aux_out", M, N, c["ldc"])
-    if k["colsum"]:
-        kw["colsum_out"], kw["colsum_atomic"] = _view(d, "colsum", 1, N, N)[0], k["colsum"] == "atomic"
+    extra = {}
+    addr = {n: flat.data_ptr() + start * flat.element_size() for n, (flat, start) in d.items()}
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if k["colsum"] == "ws":                                   # the workspaces ops.gemm_nt attaches
+        addr["colsum_ws"] = ops.scratch("nt_colsum_ws", (-(-M // 64) * N * 4,), torch.uint8, dev).data_ptr()
     if k["colstats"]:
-        kw["colstats_ws"] = torch.full((-(-M // 64), 2, N), float("nan"), dtype=torch.float32, device="cuda")
+        stats = torch.full((-(-M // 64), 2, N), float("nan"), dtype=torch.float32, device="cuda")
+        addr["colstats_ws"] = stats.data_ptr()
+    sk = ops.nt_sk_workspace(dev)
+    addr["sk_ws"] = sk.data_ptr()
+    args = u.nt_args(c, dtype, addr, sk.numel())
     old = _lib.set_option("nt_flags", flags)
     try:
-        ops.gemm_nt(_view(d, "a", M, K, c["lda"]), _view(d, "b", N, K, c["ldb"]), _view(d, "C", M, N, c["ldc"]),
-                    epilogue=u.EPI_CODE[k["epi"]], accumulate=k["accumulate"], alpha=k["alpha"], split_k=c["split_k"], **kw)
+        asked = _lib.gemm_nt_route(args, 0)
+        _lib.check(_lib.lib.eoe_gemm_nt(C.byref(args), torch.cuda.current_stream().cuda_stream), "eoe_gemm_nt")
         code = _lib.get_option("nt_last_kernel")
         torch.cuda.synchronize()
     finally:
         _lib.set_option("nt_flags", old)
+    assert asked == code, f"{c['id']}: eoe_gemm_nt_route said {u.NT_KERNELS[asked]}, the launch ran {u.NT_KERNELS[code]}"
     for n in ("C", "aux_out", "colsum"):
         if n in d:
             mem[n] = (d[n][0].cpu(), d[n][1])
     if k["colstats"]:
-        extra["stats"] = kw["colstats_ws"].cpu()
+        extra["stats"] = stats.cpu()
     return code, extra
 
 
