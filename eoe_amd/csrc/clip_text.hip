@@ -2,7 +2,7 @@
 //   * causal multi-head attention (the mask of CLIP.build_attention_mask, model.py:284-290) over up to 128 tokens, head dim 64;
 //   * the token embedding gather + positional embedding (model.py:345-347) into the fp32 residual stream;
 //   * the EOT head: first-occurrence argmax of the token ids (text.argmax(dim=-1), model.py:354) and ln_final of that row only;
-//   * a LayerNorm over rows of any width D % 64 == 0 (eoe_layernorm_fwd serves D % 256 == 0 only).
+//   * a LayerNorm over rows of any width D % 64 == 0 (the driver calls eoe_layernorm_fwd at D % 256 == 0 and this one elsewhere).
 // The layer chain itself (LayerNorm, GEMMs with their epilogues) is eoe_clip_text_fwd in clip_text_driver.cpp.
 //
 // Attention: one wavefront per (sequence, head, 64-query block).  The products follow attn_fwd_kernel (attention.hip) on the fragment

@@ -241,11 +241,20 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
 // one wavefront per row; D <= 64 * 4 * LN_MAXV
 constexpr int LN_MAXV = 4;   // float4 per lane -> D <= 1024
 
+// A lane's float4 groups sit at columns i * 256 + lane * 4, i < NV = ceil(D / 256).  TAIL: D is a multiple of 64 but not of 256, and of
+// the last group only the lanes with a column below D (16, 32 or 48 of them) take part -- `act`, the same for every row of a lane.  The
+// others load and store nothing and add zeros to the wave's sums, so every lane stays in the reductions.  With TAIL = false the test
+// folds away at compile time: the multiples of 256 keep the code they had.
+template <int NV, bool TAIL>
+__device__ __forceinline__ bool ln_tail_act(int lane, int D) { return !TAIL || (NV - 1) * 256 + lane * 4 < D; }
+template <int NV, bool TAIL>
+__device__ __forceinline__ bool ln_on(int i, bool act) { return !TAIL || i < NV - 1 || act; }
+
 struct RowStats { float mean, rstd; };
 
-template <int NV>
-__device__ __forceinline__ RowStats row_stats(const f32x4 (&v)[NV], int D, int lane, float eps) {
-    constexpr int nv = NV;
+// (v of a lane outside the tail is zero)
+template <int NV, bool TAIL>
+__device__ __forceinline__ RowStats row_stats(const f32x4 (&v)[NV], int D, bool act, float eps) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -254,7 +263,7 @@ __device__ __forceinline__ RowStats row_stats(const f32x4 (&v)[NV], int D, int l
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-        {
+        if (ln_on<NV, TAIL>(i, act)) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float d = v[i][r] - mean;
@@ -265,14 +274,15 @@ __device__ __forceinline__ RowStats row_stats(const f32x4 (&v)[NV], int D, int l
     return {mean, 1.0f / sqrtf(var + eps)};
 }
 
-template <typename T, int NV>
+template <typename T, int NV, bool TAIL>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                      const float* __restrict__ beta, void* __restrict__ y, float* __restrict__ stats,
                                      int rows, int D, float eps, int out_f32) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= rows) return;
-    constexpr int nv = NV;    // float4 groups per lane (D = 256 * NV)
+    constexpr int nv = NV;    // float4 groups per lane (D = 256 * NV, or less by 64 .. 192 columns with TAIL)
+    const bool act = ln_tail_act<NV, TAIL>(lane, D);
     f32x4 v[NV], gv[NV], bv[NV];
     const float* xr = x + (size_t)row * ldx;
     // gamma / beta with the row (round 4): loaded where they are used, each pair sat behind s_waitcnt vmcnt(0) -- which also waits for the
@@ -280,18 +290,22 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < NV; ++i)
         if (i < nv) {
-            v[i] = *(const f32x4*)(xr + i * 256 + lane * 4);
-            gv[i] = *(const f32x4*)(gamma + i * 256 + lane * 4);
-            bv[i] = *(const f32x4*)(beta + i * 256 + lane * 4);
+            if (ln_on<NV, TAIL>(i, act)) {
+                v[i] = *(const f32x4*)(xr + i * 256 + lane * 4);
+                gv[i] = *(const f32x4*)(gamma + i * 256 + lane * 4);
+                bv[i] = *(const f32x4*)(beta + i * 256 + lane * 4);
+            } else {
+                v[i] = gv[i] = bv[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
         }
-    const RowStats st = row_stats<NV>(v, D, lane, eps);
+    const RowStats st = row_stats<NV, TAIL>(v, D, act, eps);
     if (stats && lane == 0) {
         stats[row * 2] = st.mean;
         stats[row * 2 + 1] = st.rstd;
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-        if (i < nv) {
+        if (i < nv && ln_on<NV, TAIL>(i, act)) {
             const int c = i * 256 + lane * 4;
             const f32x4 g = gv[i], b = bv[i];
             float o[4];
@@ -309,7 +323,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 // (round 4: `dy_f32` and `dres` are template parameters.  As run-time branches around the loads they made hipcc emit every conditional load as
 //  load -> s_waitcnt vmcnt(0) -> use -- and vmcnt(0) also waits for the row's earlier STORES: a row was ~7 dependent HBM round trips.  Now the
 //  row's 3 NV + 1 loads are issued back to back ahead of the first use.)
-template <typename T, int NV, bool DYF32, bool DRES>
+template <typename T, int NV, bool DYF32, bool DRES, bool TAIL>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NV <= 3 ? 4 : 2, NV <= 3 ? 4 : 2))) void layernorm_bwd_kernel(const void* __restrict__ dy, const float* __restrict__ x, int ldx,
                                      const float* __restrict__ stats, const float* __restrict__ gamma,
                                      const float* __restrict__ dres, float* __restrict__ dx_out, int ld_out,
@@ -322,13 +336,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NV <= 3 ? 4
     // the wave index as a scalar: the row, and with it every row pointer, lives in SGPRs and a lane's address is one 32-bit offset
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     constexpr int nv = NV;
+    const bool act = ln_tail_act<NV, TAIL>(lane, D);
     f32x4 ag[NV], ab[NV], ax[NV], gm[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         ag[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
         ab[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
         ax[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gm[i] = *(const f32x4*)(gamma + i * 256 + lane * 4);
+        if (ln_on<NV, TAIL>(i, act)) gm[i] = *(const f32x4*)(gamma + i * 256 + lane * 4);
     }
     for (int row = blockIdx.x * NW + wave; row < rows; row += gridDim.x * NW) {
         f32x4 df[NV], xv[NV], rv[NV];
@@ -336,6 +351,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NV <= 3 ? 4
         const f32x2 st = *(const f32x2*)(stats + row * 2);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
+            if (!ln_on<NV, TAIL>(i, act)) continue;      // one test around the tail group's loads: they still issue back to back
             const int c = i * 256 + lane * 4;
             if (DYF32) df[i] = *(const f32x4*)((const float*)dy + (size_t)row * D + c);
             else dh[i] = *(const u32x2*)((const T*)dy + (size_t)row * D + c);
@@ -354,6 +370,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NV <= 3 ? 4
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
+            if (!ln_on<NV, TAIL>(i, act)) continue;
             const f32x4 d = dval(i);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -368,6 +385,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NV <= 3 ? 4
         s2 = wave_sum(s2) / D;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
+            if (!ln_on<NV, TAIL>(i, act)) continue;
             const int c = i * 256 + lane * 4;
             const f32x4 d = dval(i);
             float o[4];
@@ -393,7 +411,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NV <= 3 ? 4
     if (!dgamma && !dxsum) return;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-        if (i < nv) {
+        if (i < nv && ln_on<NV, TAIL>(i, act)) {
             // 16-byte stores (four scalar stores per lane at a 16-B lane stride were a 4-way bank conflict each).
             // (round 2: software-pipelining the wave's rows -- next row's loads ahead of this row's reductions -- raised the
             //  kernel to 174 VGPRs = one workgroup per CU and measured the same 0.87 ms / step; reverted)
@@ -483,7 +501,7 @@ __global__ __launch_bounds__(1024) void multi_reduce_kernel(JOBS jobs) {
 
 // ------------------------------------------------------------------------------------------ embed + ln_pre
 // one wavefront per token row: x0 = (l == 0 ? cls : tok[n*(L-1) + l-1]) + pos[l];  y = LN(x0)
-template <int NV>
+template <int NV, bool TAIL>
 __global__ __launch_bounds__(256) void embed_lnpre_fwd_kernel(const float* __restrict__ tok, const float* __restrict__ cls,
                                        const float* __restrict__ pos, const float* __restrict__ gamma,
                                        const float* __restrict__ beta, float* __restrict__ x0,
@@ -494,23 +512,28 @@ __global__ __launch_bounds__(256) void embed_lnpre_fwd_kernel(const float* __res
     if (row >= n * L) return;
     const int img = row / L, l = row % L;
     constexpr int nv = NV;
+    const bool act = ln_tail_act<NV, TAIL>(lane, D);
     const float* src = (l == 0) ? cls : tok + ((size_t)img * (L - 1) + (l - 1)) * D;
     f32x4 v[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i)
         if (i < nv) {
             const int c = i * 256 + lane * 4;
-            v[i] = *(const f32x4*)(src + c) + *(const f32x4*)(pos + (size_t)l * D + c);
-            *(f32x4*)(x0 + (size_t)row * D + c) = v[i];
+            if (ln_on<NV, TAIL>(i, act)) {
+                v[i] = *(const f32x4*)(src + c) + *(const f32x4*)(pos + (size_t)l * D + c);
+                *(f32x4*)(x0 + (size_t)row * D + c) = v[i];
+            } else {
+                v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
         }
-    const RowStats st = row_stats<NV>(v, D, lane, eps);
+    const RowStats st = row_stats<NV, TAIL>(v, D, act, eps);
     if (lane == 0) {
         stats[row * 2] = st.mean;
         stats[row * 2 + 1] = st.rstd;
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-        if (i < nv) {
+        if (i < nv && ln_on<NV, TAIL>(i, act)) {
             const int c = i * 256 + lane * 4;
             const f32x4 g = *(const f32x4*)(gamma + c), b = *(const f32x4*)(beta + c);
             f32x4 o;
@@ -522,7 +545,7 @@ __global__ __launch_bounds__(256) void embed_lnpre_fwd_kernel(const float* __res
 
 // backward: one block per token position l (grid = L), waves stride over the images; dpos[l] and (l == 0)
 // dcls are complete sums over the batch -> plain stores/adds without atomics; dgamma/dbeta via atomics.
-template <typename T, int NV>
+template <typename T, int NV, bool TAIL>
 __global__ __launch_bounds__(256) void embed_lnpre_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x0,
                                        const float* __restrict__ stats, const float* __restrict__ gamma,
                                        T* __restrict__ dtok, float* __restrict__ dcls, float* __restrict__ dpos,
@@ -532,11 +555,12 @@ __global__ __launch_bounds__(256) void embed_lnpre_bwd_kernel(const float* __res
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l = blockIdx.x;
     constexpr int nv = NV;
+    const bool act = ln_tail_act<NV, TAIL>(lane, D);
     f32x4 ag[NV], ab[NV], ap[NV], gm[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         ag[i] = ab[i] = ap[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (i < nv) gm[i] = *(const f32x4*)(gamma + i * 256 + lane * 4);
+        if (i < nv && ln_on<NV, TAIL>(i, act)) gm[i] = *(const f32x4*)(gamma + i * 256 + lane * 4);
     }
     for (int img = wave; img < n; img += 4) {
         const size_t row = (size_t)img * L + l;
@@ -545,7 +569,7 @@ __global__ __launch_bounds__(256) void embed_lnpre_bwd_kernel(const float* __res
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i)
-            if (i < nv) {
+            if (i < nv && ln_on<NV, TAIL>(i, act)) {
                 const int c = i * 256 + lane * 4;
                 const f32x4 d = *(const f32x4*)(dy + row * D + c);
                 const f32x4 xv = *(const f32x4*)(x0 + row * D + c);
@@ -563,7 +587,7 @@ __global__ __launch_bounds__(256) void embed_lnpre_bwd_kernel(const float* __res
         s2 = wave_sum(s2) / D;
 #pragma unroll
         for (int i = 0; i < NV; ++i)
-            if (i < nv) {
+            if (i < nv && ln_on<NV, TAIL>(i, act)) {
                 const int c = i * 256 + lane * 4;
                 float o[4];
 #pragma unroll
@@ -577,7 +601,7 @@ __global__ __launch_bounds__(256) void embed_lnpre_bwd_kernel(const float* __res
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-        if (i < nv) {
+        if (i < nv && ln_on<NV, TAIL>(i, act)) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 red[0][wave][i * 256 + lane * 4 + r] = ag[i][r];
@@ -1273,15 +1297,21 @@ __global__ __launch_bounds__(256) void grads_nonfinite_kernel(const float* __res
 
 }  // namespace
 
-#define DISPATCH_NV(D, ...)                                      \
-    do {                                                         \
-        switch ((D) / 256) {                                     \
+// NV = ceil(D / 256) float4 groups per lane; TAIL where the last one is partial (D % 256 != 0; the callers checked D % 64 == 0, 64 <= D <= 1024)
+#define DISPATCH_NV_(D, ...)                                     \
+        switch (((D) + 255) / 256) {                             \
             case 1: { constexpr int NV = 1; __VA_ARGS__; } break; \
             case 2: { constexpr int NV = 2; __VA_ARGS__; } break; \
             case 3: { constexpr int NV = 3; __VA_ARGS__; } break; \
             default: { constexpr int NV = 4; __VA_ARGS__; } break; \
-        }                                                        \
+        }
+#define DISPATCH_NV(D, ...)                                      \
+    do {                                                         \
+        if ((D) % 256 == 0) { constexpr bool TAIL = false; DISPATCH_NV_(D, __VA_ARGS__) } \
+        else { constexpr bool TAIL = true; DISPATCH_NV_(D, __VA_ARGS__) } \
     } while (0)
+// the width every LayerNorm / embed entry point takes
+#define EOE_LN_WIDTH_OK(D) ((D) >= 64 && (D) % 64 == 0 && (D) <= 1024)
 
 #define DISPATCH_T(dtype, ...)                                  \
     do {                                                        \
@@ -1361,9 +1391,9 @@ extern "C" int eoe_patchify(const float* x, const float* mean, const float* stdv
 extern "C" int eoe_layernorm_fwd(const float* x, int ldx, const float* gamma, const float* beta, void* y,
                                  float* stats, int rows, int D, float eps, int dtype, int out_f32, void* stream) {
     EOE_CHECK_ARG(x && gamma && beta && y && rows > 0, "layernorm_fwd: bad args");
-    EOE_CHECK_ARG(D % 256 == 0 && D <= 1024 && ldx % 4 == 0, "layernorm: D must be a multiple of 256, <= 1024");
+    EOE_CHECK_ARG(EOE_LN_WIDTH_OK(D) && ldx % 4 == 0, "layernorm: D must be a multiple of 64, <= 1024 (and ldx a multiple of 4)");
     ProfScope ps("layernorm_fwd", 0, (4.0 + (out_f32 ? 4.0 : 2.0)) * rows * D, stream);
-    DISPATCH_T(dtype, DISPATCH_NV(D, hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV>), dim3(cdiv(rows, 4)), dim3(256), 0,
+    DISPATCH_T(dtype, DISPATCH_NV(D, hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV, TAIL>), dim3(cdiv(rows, 4)), dim3(256), 0,
                                          (hipStream_t)stream, x, ldx, gamma, beta, y, stats, rows, D, eps, out_f32)));
     EOE_CHECK_LAUNCH("layernorm_fwd");
     return 0;
@@ -1374,7 +1404,7 @@ extern "C" int eoe_layernorm_bwd(const void* dy, int dy_f32, const float* x, int
                                  float* dgamma, float* dbeta, float* dxsum, float* red_scratch, int rows, int D, int dtype,
                                  void* stream) {
     EOE_CHECK_ARG(dy && x && stats && gamma && dx_out && rows > 0, "layernorm_bwd: bad args");
-    EOE_CHECK_ARG(D % 256 == 0 && D <= 1024 && ldx % 4 == 0 && ld_out % 4 == 0, "layernorm: D must be a multiple of 256, <= 1024");
+    EOE_CHECK_ARG(EOE_LN_WIDTH_OK(D) && ldx % 4 == 0 && ld_out % 4 == 0, "layernorm: D must be a multiple of 64, <= 1024 (and ldx, ld_out multiples of 4)");
     EOE_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "layernorm_bwd: dgamma/dbeta must both be given or both NULL");
     ProfScope ps("layernorm_bwd", 0, ((dy_f32 ? 4.0 : 2.0) + 4.0 + (dres ? 4.0 : 0.0) + 4.0 + (dx16 ? 2.0 : 0.0)) * rows * D, stream);
     int grid = cdiv(rows, 8);
@@ -1382,8 +1412,8 @@ extern "C" int eoe_layernorm_bwd(const void* dy, int dy_f32, const float* x, int
     float* part = (dgamma || dxsum) ? red_scratch : nullptr;
     // (the attribute once per instantiation, not per launch)
 #define EOE_LNB_LAUNCH(F, R)                                                                                                           \
-    { static bool once = (hipFuncSetAttribute((const void*)layernorm_bwd_kernel<T, NV, F, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 256 * NV * 4), true); (void)once; } \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, F, R>), dim3(grid), dim3(512), 3 * 8 * 256 * NV * 4, (hipStream_t)stream, dy, x, ldx, stats, gamma, \
+    { static bool once = (hipFuncSetAttribute((const void*)layernorm_bwd_kernel<T, NV, F, R, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 256 * NV * 4), true); (void)once; } \
+    hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, F, R, TAIL>), dim3(grid), dim3(512), 3 * 8 * 256 * NV * 4, (hipStream_t)stream, dy, x, ldx, stats, gamma, \
                        dres, dx_out, ld_out, (T*)dx16, dgamma, dbeta, dxsum, part, rows, D)
     DISPATCH_T(dtype, DISPATCH_NV(D, {
         if (dy_f32) { if (dres) { EOE_LNB_LAUNCH(true, true); } else { EOE_LNB_LAUNCH(true, false); } }
@@ -1476,8 +1506,8 @@ extern "C" int eoe_embed_lnpre_fwd(const float* tok, const float* cls, const flo
                                    const float* beta, float* x0, float* y, float* stats, int n, int L, int D,
                                    float eps, void* stream) {
     EOE_CHECK_ARG(tok && cls && pos && gamma && beta && x0 && y && stats && n > 0 && L > 1, "embed_lnpre_fwd: bad args");
-    EOE_CHECK_ARG(D % 256 == 0 && D <= 1024, "embed_lnpre: D must be a multiple of 256, <= 1024");
-    DISPATCH_NV(D, hipLaunchKernelGGL((embed_lnpre_fwd_kernel<NV>), dim3(cdiv(n * L, 4)), dim3(256), 0, (hipStream_t)stream, tok, cls, pos,
+    EOE_CHECK_ARG(EOE_LN_WIDTH_OK(D), "embed_lnpre: D must be a multiple of 64, <= 1024");
+    DISPATCH_NV(D, hipLaunchKernelGGL((embed_lnpre_fwd_kernel<NV, TAIL>), dim3(cdiv(n * L, 4)), dim3(256), 0, (hipStream_t)stream, tok, cls, pos,
                        gamma, beta, x0, y, stats, n, L, D, eps));
     EOE_CHECK_LAUNCH("embed_lnpre_fwd");
     return 0;
@@ -1488,8 +1518,8 @@ extern "C" int eoe_embed_lnpre_bwd(const float* dy, const float* x0, const float
                                    int L, int D, int dtype, void* stream) {
     EOE_CHECK_ARG(dy && x0 && stats && gamma && dtok && dcls && dpos && dgamma && dbeta && n > 0 && L > 1,
                   "embed_lnpre_bwd: bad args");
-    EOE_CHECK_ARG(D % 256 == 0 && D <= 1024, "embed_lnpre: D must be a multiple of 256, <= 1024");
-    DISPATCH_T(dtype, DISPATCH_NV(D, hipLaunchKernelGGL((embed_lnpre_bwd_kernel<T, NV>), dim3(L), dim3(256), 0, (hipStream_t)stream, dy, x0,
+    EOE_CHECK_ARG(EOE_LN_WIDTH_OK(D), "embed_lnpre: D must be a multiple of 64, <= 1024");
+    DISPATCH_T(dtype, DISPATCH_NV(D, hipLaunchKernelGGL((embed_lnpre_bwd_kernel<T, NV, TAIL>), dim3(L), dim3(256), 0, (hipStream_t)stream, dy, x0,
                                          stats, gamma, (T*)dtok, dcls, dpos, dgamma, dbeta, scratch, n, L, D)));
     EOE_CHECK_LAUNCH("embed_lnpre_bwd");
     if (scratch) EOE_TRY(eoe_finish_reduce(scratch, L, 2 * D, D, dgamma, dbeta, nullptr, 1, stream));

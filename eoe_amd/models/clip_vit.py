@@ -96,17 +96,16 @@ class Transformer(nn.Module):
 
 def check_vit_geometry(input_resolution: int, patch_size: int, width: int, heads: int):
     """the image-tower geometries the kernels serve, checked where the model is built instead of in its first forward: patchify takes
-    patch % 4 == 0, the LayerNorm and embed kernels widths up to 1024 (see below), attention head dim 64 and at most ops.ATTN_LONG_MAX_L
+    patch % 4 == 0, the LayerNorm and embed kernels every width % 64 == 0 up to 1024, attention head dim 64 and at most ops.ATTN_LONG_MAX_L
     tokens (the short kernels up to 64 tokens, csrc/attention_long.hip above)"""
     if patch_size <= 0 or patch_size % 4 != 0:
         raise NotImplementedError(f"patch size {patch_size}: the patch-extraction kernel needs patch_size % 4 == 0 (ViT-L/14 is not served)")
     if input_resolution < patch_size or input_resolution % patch_size != 0:
         raise NotImplementedError(f"input resolution {input_resolution} is not a positive multiple of the patch size {patch_size}")
-    # (width % 256 == 0 is what the LayerNorm and embed kernels serve, but a narrower tower is a legitimate parameter CONTAINER -- the
-    #  fp16-weights fixture of the reference is written at width 128 -- so only what no container needs is refused here; a width the
-    #  kernels do not take still fails in the first forward, naming the kernel)
+    # (every multiple of 64 up to 1024 runs: 192 / 3 heads is ViT-Ti, 384 / 6 heads ViT-S; where the width is no multiple of 256 the
+    #  LayerNorm and embed kernels predicate the last 256-column group of a row, csrc/elementwise.hip)
     if width > 1024 or width % 64 != 0:
-        raise NotImplementedError(f"width {width}: the LayerNorm and embed kernels need width % 256 == 0 and width <= 1024")
+        raise NotImplementedError(f"width {width}: the LayerNorm and embed kernels need width % 64 == 0 and width <= 1024")
     if heads * 64 != width:
         raise NotImplementedError(f"{heads} heads at width {width}: the attention kernels are written for head dim 64 (heads = width / 64)")
     tokens = (input_resolution // patch_size) ** 2 + 1
@@ -116,7 +115,10 @@ def check_vit_geometry(input_resolution: int, patch_size: int, width: int, heads
 
 class VisualTransformer(nn.Module):
     """model.py:202-236.  `normalize=(mean, std)` optionally fuses the trainer's per-channel Normalize
-    (`ad_trainer.py:413-425`, `transformations.py:126-138`) into the patch-extraction kernel."""
+    (`ad_trainer.py:413-425`, `transformations.py:126-138`) into the patch-extraction kernel.
+
+    Geometries (`check_vit_geometry`): patch % 4 == 0, width any multiple of 64 up to 1024 with heads = width / 64 (ViT-Ti 192 / 3,
+    ViT-S 384 / 6, ViT-B 768 / 12, ViT-L's 1024 / 16), at most ops.ATTN_LONG_MAX_L tokens."""
 
     def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int, output_dim: int):
         super().__init__()

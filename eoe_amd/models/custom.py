@@ -10,8 +10,8 @@ from .resnet import WideResNet
 
 class ClipViTB32Custom(CustomNet):
     """feature_model = CLIP ViT-B/32 image tower (224, patch 32, width 768, 12 layers, 12 heads, 512-d) by default; `patch_size`, `width`
-    and `output_dim` give the other ViT towers of CLIP (ViT-B/16: patch_size=16; heads = width / 64), within
-    clip_vit.check_vit_geometry"""
+    and `output_dim` give the other ViT towers of CLIP (ViT-B/16: patch_size=16; heads = width / 64) and the narrow towers trained from
+    scratch on small images (ViT-Ti: width=192, ViT-S: width=384; any multiple of 64 up to 1024), within clip_vit.check_vit_geometry"""
 
     def __init__(self, prediction_head: bool = True, clf: bool = False, freeze: bool = False, layers: int = 12,
                  input_resolution: int = 224, patch_size: int = 32, width: int = 768, output_dim: int = 512):

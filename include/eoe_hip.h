@@ -163,7 +163,7 @@ int eoe_embed_lnpre_bwd(const float* dy, const float* x0, const float* stats, co
 
 /* LayerNorm over the last dim (clip/model.py:153-159, fp32 statistics, biased variance):
  * x fp32 [rows, D] (row stride ldx elements) -> y 16-bit [rows, D] (GEMM operand) or fp32 if out_f32,
- * stats [rows, 2]. */
+ * stats [rows, 2].  D: any multiple of 64 from 64 to 1024, here and in eoe_layernorm_bwd / eoe_embed_lnpre_fwd / _bwd. */
 int eoe_layernorm_fwd(const float* x, int ldx, const float* gamma, const float* beta, void* y, float* stats,
                       int rows, int D, float eps, int dtype, int out_f32, void* stream);
 /* dx_out[r, :] (fp32, row stride ld_out) = (dres ? dres[r, :] : 0) + LN'(dy)[r, :];  dx16 (optional) = 16-bit
