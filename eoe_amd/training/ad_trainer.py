@@ -26,6 +26,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
   * `curves=True` makes the trainer keep what the reference always keeps: the whole ROC of a training epoch (the last one is returned) and the ROC and
     precision-recall curve of the evaluation (:452-455, 516-522), counted on the device (`eoe_rank_curves`), and the per-class
     "mean" curves (`logger.py:94-122`) in `trainer.curves`.  The default keeps the scores alone and does nothing else.
+  * `histograms=True` logs what the reference always logs to TensorBoard: after every training epoch the histograms of the epoch's
+    anomaly scores, normal half and outlier-exposure half (:458-465), after an evaluation those of the nominal and the anomalous test
+    scores (:541-546), bucketed on the device (`eoe_score_hist`), kept in `trainer.histograms` and handed to
+    `logger.add_histogram` under the reference's tags.  Off by default.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -38,7 +42,8 @@ import numpy as np
 import torch
 
 from .. import ops, parallel
-from ..metrics import ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve
+from ..metrics import (ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve,
+                       score_histograms)
 from ..msm import apply_msms, check_supported
 from ..normalize import GcnNormalize
 from ..optim import FusedAdam
@@ -64,6 +69,7 @@ class JsonLogger:
         # for BatchNorm encoders rank 0's running statistics are the ones kept)
         rank0 = int(os.environ.get("RANK", "0")) == 0
         self.dir, self.active = logdir, active and logdir is not None and rank0
+        self.histograms = {}                                # tag -> {step: eoe_amd.metrics.Histogram} (add_histogram)
         if self.active:
             os.makedirs(os.path.join(logdir, "snapshots"), exist_ok=True)
 
@@ -79,6 +85,14 @@ class JsonLogger:
 
     def add_scalar(self, *a, **k):
         pass
+
+    def add_histogram(self, tag: str, hist, step: int = 0):
+        """`SummaryWriter.add_histogram(tag, values, step)` for a histogram that is already made (`eoe_amd.metrics.score_histogram`):
+        kept in `self.histograms[tag][step]`, and an active logger rewrites `<dir>/histograms.json`, {tag: {step: the seven
+        fields}} of everything added so far (JSON turns the step into a string).  No TensorBoard file is written."""
+        self.histograms.setdefault(tag, {})[int(step)] = hist
+        if self.active:
+            self.logjson("histograms", {t: {str(s): h.as_dict() for s, h in steps.items()} for t, steps in self.histograms.items()})
 
     def logimg(self, name: str, src, rows=None, nrow: int = 8, pad: int = 2, rowheaders=None, row_sep_at=(None, None),
                maxres: int = 128, step: int = None, mark=None, crop=None) -> np.ndarray:
@@ -120,7 +134,7 @@ class ADTrainer(ABC):
                  device: Union[str, torch.device] = "cuda", oe_limit_samples=np.inf, oe_limit_classes=np.inf,
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
-                 previews: bool = False):
+                 previews: bool = False, histograms: bool = False):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -139,7 +153,16 @@ class ADTrainer(ABC):
         the train loader's output) and `eval_cls{c}-{cstr}_preview` (20 per label of the test loader's) as the reference does
         (`ad_trainer.py:386-393, 486-493`), through `ds.preview` and `logger.logimg`: one row per label, the labels' sample counts as
         `rowheaders`.  The source draws the preview from a private generator, so the training that follows is unchanged.  Default
-        off: nothing runs, nothing is drawn, the same files as before."""
+        off: nothing runs, nothing is drawn, the same files as before.
+
+        `histograms=True`: after each training epoch's NaN check `train_cls` makes the two histograms of the epoch's scores (under
+        data parallelism: the gathered ones), label 0 and label 1, and `eval_cls` the two of the test scores
+        (`eoe_amd.metrics.score_histograms`: one launch sequence per pair for device scores, only counts and five scalars come back).
+        They are kept in `self.histograms` = {tag: {step: `metrics.Histogram`}} and handed to `logger.add_histogram(tag, hist, step)`
+        under the reference's tags and steps (`ad_trainer.py:458-465, 541-546`): `Training: CLS{cls} SEED{seed} anomaly_scores normal`
+        / `... anomalous` at step `ep`, `Eval: (SD{seed}) anomaly_scores cls{cls} nominal` / `... anomalous` at step 0.  A label without
+        scores is skipped (the reference's `make_histogram` would raise).  `run` starts with an empty `self.histograms`.  Default off:
+        no launch, no file, the same return values and files as before."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -176,6 +199,8 @@ class ADTrainer(ABC):
         self._gcn = None                                    # the task's GcnNormalize, if its source is in that mode (_normalize_hook)
         self.with_curves = bool(curves)
         self.curves = None                                  # filled by run() when with_curves
+        self.with_histograms = bool(histograms)
+        self.histograms = {}                                # tag -> {step: Histogram}, filled by train_cls / eval_cls when with_histograms
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -288,6 +313,7 @@ class ADTrainer(ABC):
         models, train_rocs = [[] for _ in range(n_cls)], [[] for _ in range(n_cls)]
         eval_rocs, eval_prcs = [[] for _ in range(n_cls)], [[] for _ in range(n_cls)]
         means = {k: [None] * n_cls for k in ("mean_train_rocs", "mean_eval_rocs", "mean_eval_prcs")}
+        self.histograms = {}
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
@@ -406,6 +432,16 @@ class ADTrainer(ABC):
         heads = [str(stats[k]) for k in sorted(stats)] if train else [f"{k}: {v}" for k, v in sorted(stats.items())]
         self.logger.logimg(name, prev, nrow=max(prev.shape[0] // len(stats), 1), rowheaders=heads)
 
+    def _log_histograms(self, la: torch.Tensor, sc: torch.Tensor, tag0: str, tag1: str, step: int):
+        """the histograms of the scores with label 0 and with label 1 (`histograms=True` only): kept and handed to the logger; a
+        label without scores, or no scores at all, is skipped"""
+        if sc.numel() == 0:
+            return
+        for tag, hist in zip((tag0, tag1), score_histograms(la, sc)):
+            if hist is not None:
+                self.histograms.setdefault(tag, {})[step] = hist
+                self.logger.add_histogram(tag, hist, step)
+
     def make_optimizer(self, model: torch.nn.Module):
         """Adam for every encoder (ad_trainer.py:383); the CLIP objective overrides this with SGD-Nesterov (:380-381)"""
         return FusedAdam(model.parameters(), lr=self.lr, weight_decay=self.wdk, amsgrad=False)
@@ -517,6 +553,9 @@ class ADTrainer(ABC):
                 self.last_scores.append((la, sc))
                 if bool(torch.isnan(sc).any()):
                     raise NanGradientsError()                                                           # :448-449
+                if self.with_histograms:                                                                # :458-465
+                    self._log_histograms(la, sc, f"Training: CLS{cls} SEED{seed} anomaly_scores normal",
+                                         f"Training: CLS{cls} SEED{seed} anomaly_scores anomalous", ep)
                 if bool((la == 1).any()):
                     # the epoch's AUC from the GPU-resident scores (eoe_auc_ap: exact pair counts), no host copy of the scores
                     cls_roc = ROC(auc_ap_device(la, sc)[0] if sc.is_cuda else roc_auc(la.cpu().numpy(), sc.cpu().numpy()))   # :452-455
@@ -583,6 +622,9 @@ class ADTrainer(ABC):
                                f'{cls_prc.avg_prec * 100:04.2f}% average precision (seed {seed}).')
         else:
             cls_roc = cls_prc = None
+        if self.with_histograms:                                                                        # :541-546
+            self._log_histograms(la_t, sc_t, f"Eval: (SD{seed}) anomaly_scores cls{cls} nominal",
+                                 f"Eval: (SD{seed}) anomaly_scores cls{cls} anomalous", 0)
         self.logger.logjson(f"eval_cls{cls}_it{seed}_anomaly_scores", {int(k): float(v) for k, v in zip(idc, sc)})
         model.cpu()
         return cls_roc, cls_prc

@@ -862,6 +862,23 @@ size_t eoe_rank_curves_scratch_bytes(int n);
 int eoe_rank_curves(const float* scores, const int64_t* labels, int64_t positive_label, int n, int drop_intermediate,
                     int64_t* out_fps, int64_t* out_tps, float* out_thr, int64_t* out_roc_fps, int64_t* out_roc_tps, float* out_roc_thr,
                     int32_t* out_counts, void* scratch, void* stream);
+/* The epoch's score histograms (ad_trainer.py:458-465, 541-546: SummaryWriter.add_histogram on the scores of label 0 and of label 1;
+ * csrc/hist.hip): for both label groups in one pass, what np.histogram(values, bins=edges) counts and the five scalars TensorBoard
+ * stores with it.  Bin b = [edges[b], edges[b+1]), the last bin closed on both sides, a value outside [edges[0], edges[E-1]] in no
+ * bin; scores are compared as float64 against the table (a binary search; -0.0 is 0.0).
+ *   scores fp32 [n] DEVICE; labels int64 [n] DEVICE: group 0 = label 0, group 1 = label 1, any other label in neither group;
+ *   labels NULL: every score is in group 0 and group 1 is empty.  n >= 1.
+ *   edges_host / edges: the same float64 table [E] in HOST memory (checked here: finite, strictly ascending) and in DEVICE memory
+ *   (read by the kernel; the caller uploads it once per device).  2 <= E <= 4001 (the table and both groups' counters share LDS).
+ *   out_counts int32 [2][E-1] DEVICE (cleared here); out_stats fp64 [2][5] DEVICE, 8-byte aligned: per group count, min, max, sum and
+ *   sum of squares over ALL of the group's scores, binned or not; an empty group reports count 0 and zeros.
+ *   Counts are integer adds (LDS atomics per workgroup, integer atomics into out_counts); the fp64 sums use no floating-point atomic
+ *   and a fixed order: two runs give the same bits.  Non-finite scores are the caller's to reject (they land in no bin).
+ *   scratch: eoe_score_hist_scratch_bytes(n) bytes (0 for n < 1), 8-byte aligned, may be dirty.  Three enqueues on `stream` (a memset
+ *   and two launches). */
+size_t eoe_score_hist_scratch_bytes(int n);
+int eoe_score_hist(const float* scores, const int64_t* labels, int n, const double* edges_host, const double* edges, int E,
+                   int32_t* out_counts, double* out_stats, void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
