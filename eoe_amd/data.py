@@ -1135,12 +1135,7 @@ class ResidentImageSource:
             class _Test:
                 def __iter__(s):
                     for lo in range(0, len(outer.test_y), batch_size):
-                        idx = torch.arange(lo, min(lo + batch_size, len(outer.test_y)))
-                        p = torch.zeros((len(idx), 4), dtype=torch.int32)
-                        p[:, 0] = idx
-                        x = augment_resize_batch(outer.test, p.to(outer.test.device), outer.test.shape[1], outer.clip_preprocessing,
-                                                 *outer._norm_args(), True, 0.0, 0)
-                        yield x, outer.test_y[idx], idx
+                        yield outer._clip_test_batch(torch.arange(lo, min(lo + batch_size, len(outer.test_y))))
 
                 def __len__(s):
                     return math.ceil(len(outer.test_y) / batch_size)
@@ -1166,6 +1161,26 @@ class ResidentImageSource:
             p = torch.stack([idx, torch.full_like(idx, (Hs - side) // 2), torch.full_like(idx, (Ws - side) // 2),
                              torch.zeros_like(idx)], dim=1).to(torch.int32).to(self.test.device)
         return augment_batch(self.test, p, (side, side), *self._norm_args(), True, 0.0, 0), self.test_y[idx], idx
+
+    def _clip_test_batch(self, idx):
+        """(images, labels, indices) of the listed test rows under an active clip_preprocessing stage: CLIP's transform of the whole
+        image (an identity "crop"), no noise"""
+        p = torch.zeros((len(idx), 4), dtype=torch.int32)
+        p[:, 0] = idx
+        x = augment_resize_batch(self.test, p.to(self.test.device), self.test.shape[1], self.clip_preprocessing, *self._norm_args(), True,
+                                 0.0, 0)
+        return x, self.test_y[idx], idx
+
+    def test_images(self, rows):
+        """the test loader's images of the listed test rows, in the listed order (repeats allowed): fp32 NCHW on the set's device, by
+        the route `preview(train=False)` takes -- `_test_batch`, or the loader's output under an active clip_preprocessing stage.
+        Deterministic: no random draw is consumed."""
+        idx = torch.as_tensor(rows).to(torch.int64).cpu().reshape(-1)
+        if len(idx) and (int(idx.min()) < 0 or int(idx.max()) >= len(self.test_y)):
+            raise IndexError(f"test_images: rows outside the test set of {len(self.test_y)} images")
+        if self.clip_preprocessing is not None and self._clip_px(self.test.shape[1], self.test.shape[3]) is not None:
+            return self._clip_test_batch(idx)[0]
+        return self._test_batch(idx)[0]
 
     PREVIEW_SEED = 0x9E3779B1
 

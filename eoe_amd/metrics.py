@@ -8,7 +8,11 @@ score -- `eoe_rank_curves` for GPU tensors, a sort for host arrays -- and sklear
 
 The score histograms the reference logs next to them (`:458-465, 541-546`, TensorBoard's `add_histogram`) are `score_histogram` /
 `score_histograms`: integer counts over TensorBoard's fixed edges -- `eoe_score_hist` for GPU tensors, `np.histogram` for host
-arrays -- and the same trimming of the integer arrays on the host."""
+arrays -- and the same trimming of the integer arrays on the host.
+
+Which test images those numbers rest on -- per label group the highest and the lowest scores with their positions, as the reference
+ranks OE individuals in `Tree.scores_best` -- is `score_extremes`: `eoe_score_extremes` (an exact radix select) for GPU tensors, two
+stable argsorts for host arrays."""
 from typing import Optional
 
 import numpy as np
@@ -437,3 +441,129 @@ def score_histogram(scores, labels=None, label=None, bins="tensorflow"):
         return _hist_from_device(*score_hist_device(scores, None, bins), 0)
     s, _ = _hist_host_inputs(scores, None)
     return _hist_host(s, _hist_edges(bins))
+
+
+# ------------------------------------------------------------------------------------------------------ extremes
+EXTREMES_MAX_N = 1 << 20          # eoe_score_extremes: a position fits the low 20 bits of its key
+EXTREMES_MAX_K = 1024             # what one workgroup sorts in LDS
+_GROUP_NAMES = ("nominal", "anomalous")
+
+
+class Extremes:
+    """the extremes of an evaluation's scores per label group g (0: label 0, nominal; 1: label 1, anomalous): `most[g]` and `least[g]`
+    are (indices int64 ndarray, scores float32 ndarray) pairs of min(k, num[g]) entries -- the highest scores first resp. the lowest
+    first, equal scores by ascending position -- and `num[g]` the size of the group.  `most[0]` are the false alarms, `least[1]` the
+    misses."""
+
+    def __init__(self, most, least, num):
+        pair = lambda p: (np.asarray(p[0], dtype=np.int64), np.asarray(p[1], dtype=np.float32))    # noqa: E731
+        self.most, self.least = (pair(most[0]), pair(most[1])), (pair(least[0]), pair(least[1]))
+        self.num = (int(num[0]), int(num[1]))
+
+    def as_dict(self) -> dict:
+        """{"nominal": {"most": [[index, score], ...], "least": [...], "num": m}, "anomalous": {...}}: ints and floats, for JSON"""
+        rows = lambda p: [[int(i), float(v)] for i, v in zip(*p)]                                    # noqa: E731
+        return {name: {"most": rows(self.most[g]), "least": rows(self.least[g]), "num": self.num[g]} for g, name in enumerate(_GROUP_NAMES)}
+
+    def __eq__(self, other):
+        return isinstance(other, Extremes) and self.num == other.num and all(
+            np.array_equal(a[j], b[j]) and a[j].dtype == b[j].dtype
+            for a, b in zip(self.most + self.least, other.most + other.least) for j in (0, 1))
+
+    def __repr__(self):
+        return f"Extremes(num={self.num}, k={[len(p[0]) for p in self.most]})"
+
+
+def _check_extremes_k(k):
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or k < 1 or k > EXTREMES_MAX_K:
+        raise ValueError(f"k must be an integer in [1, {EXTREMES_MAX_K}], not {k!r}")
+    return int(k)
+
+
+def _extremes_host(s: np.ndarray, y: Optional[np.ndarray], k: int):
+    """the two stable argsorts per group: ((most pairs), (least pairs), (num)) over positions"""
+    most, least, num = [], [], []
+    for g in (0, 1):
+        members = np.flatnonzero(y == g) if y is not None else (np.arange(s.size) if g == 0 else np.zeros(0, np.int64))
+        sg = s[members]
+        if not np.isfinite(sg).all():
+            raise ValueError("scores contain NaN or infinity")
+        hi, lo = members[np.argsort(-sg, kind="stable")[:k]], members[np.argsort(sg, kind="stable")[:k]]
+        most.append((hi, s[hi]))
+        least.append((lo, s[lo]))
+        num.append(members.size)
+    return most, least, num
+
+
+def score_extremes_device(labels, scores, k: int = 20, scratch=None):
+    """`eoe_score_extremes` on GPU-resident scores: (idx int32 [2, 2, k], val float32 [2, 2, k], counts [m_0, m_1, non-finite]) as host
+    arrays -- [group][end] with end 0 = most, end 1 = least; the slots past min(k, m_g) hold -1 and 0.  One call (a memset and seven
+    launches) and ONE copy back of the 4 k pairs and the three counts.  `labels` None: every score in group 0.  `scratch`: a uint8 GPU
+    tensor of at least `eoe_score_extremes_scratch_bytes(n, k)` bytes to reuse (its content does not matter)."""
+    import torch
+    from ._lib import check, lib
+    if not _is_gpu_tensor(scores):
+        raise RuntimeError("score_extremes_device needs GPU tensors (score_extremes takes host arrays as they are)")
+    k = _check_extremes_k(k)
+    sc = scores.detach().reshape(-1).contiguous().float()
+    n = sc.numel()
+    la = None
+    if labels is not None:
+        la = torch.as_tensor(labels).to(sc.device).reshape(-1).contiguous().to(torch.int64)
+    if n == 0 or (la is not None and la.numel() != n):
+        raise ValueError(f"extremes need at least one score and as many labels as scores, not {n} and {None if la is None else la.numel()}")
+    if n > EXTREMES_MAX_N:
+        raise ValueError(f"eoe_score_extremes takes at most {EXTREMES_MAX_N} scores, not {n}")
+    need = lib.eoe_score_extremes_scratch_bytes(n, k)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=sc.device)
+    elif scratch.dtype != torch.uint8 or scratch.device != sc.device or scratch.numel() < need or not scratch.is_contiguous() \
+            or scratch.data_ptr() % 16:
+        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 tensor of at least {need} bytes on {sc.device}")
+    # one buffer, one copy back: 4 k positions (-1 where a list is shorter), 4 k scores, 3 counts
+    out = torch.empty(8 * k + 3, dtype=torch.int32, device=sc.device)
+    out[:4 * k] = -1
+    out[4 * k:] = 0
+    with torch.cuda.device(sc.device):
+        check(lib.eoe_score_extremes(sc.data_ptr(), la.data_ptr() if la is not None else None, n, k, out.data_ptr(),
+                                     out.data_ptr() + 16 * k, out.data_ptr() + 32 * k, scratch.data_ptr(),
+                                     torch.cuda.current_stream(sc.device).cuda_stream), "eoe_score_extremes")
+    raw = out.cpu().numpy()
+    return raw[:4 * k].reshape(2, 2, k).copy(), raw[4 * k:8 * k].view(np.float32).reshape(2, 2, k).copy(), raw[8 * k:].tolist()
+
+
+def score_extremes(labels, scores, k: int = 20, indices=None) -> Extremes:
+    """The most and the least anomalous samples per label group: for the scores with label 0 (nominal) and those with label 1
+    (anomalous) the `k` highest -- `np.argsort(-s, kind="stable")[:k]` over the group's members -- and the `k` lowest --
+    `np.argsort(s, kind="stable")[:k]` -- with equal scores (-0.0 == 0.0) in ascending position.  Scores with any other label (-1 for
+    unlabelled images) are in neither group; `labels=None` puts every score in group 0.  A `k` larger than a group returns the whole
+    group, ranked.  Scores are ranked as float32.
+
+    GPU tensors go through `eoe_score_extremes` in one call, and only the 4 k pairs and three counts come back; NumPy arrays and CPU
+    tensors take the two stable argsorts on the host.  Both give the same positions and the same score bits.
+
+    `indices` (optional, one per score) maps positions to dataset indices in the returned `indices`; the ranking itself is by position.
+    ValueError for a non-finite score among the members of a group, for k outside [1, 1024], for no scores, and for labels or
+    `indices` of another length; the device path takes at most 2^20 scores."""
+    k = _check_extremes_k(k)
+    remap = None if indices is None else np.asarray(_to_host(indices)).ravel().astype(np.int64)
+    if _is_gpu_tensor(scores):
+        if remap is not None and remap.size != scores.numel():
+            raise ValueError(f"indices must name every score: {remap.size} for {scores.numel()} scores")
+        idx, val, (m0, m1, bad) = score_extremes_device(labels, scores, k)
+        if bad:
+            raise ValueError("scores contain NaN or infinity")
+        num = (m0, m1)
+        most = [(idx[g, 0, :min(k, num[g])].astype(np.int64), val[g, 0, :min(k, num[g])]) for g in (0, 1)]
+        least = [(idx[g, 1, :min(k, num[g])].astype(np.int64), val[g, 1, :min(k, num[g])]) for g in (0, 1)]
+    else:
+        s = np.asarray(_to_host(scores)).ravel().astype(np.float32)
+        y = None if labels is None else np.asarray(_to_host(labels)).ravel()
+        if s.size == 0 or (y is not None and y.size != s.size):
+            raise ValueError(f"extremes need at least one score and as many labels as scores, not {s.size} and {None if y is None else y.size}")
+        if remap is not None and remap.size != s.size:
+            raise ValueError(f"indices must name every score: {remap.size} for {s.size} scores")
+        most, least, num = _extremes_host(s, y, k)
+    if remap is not None:
+        most, least = [(remap[i], v) for i, v in most], [(remap[i], v) for i, v in least]
+    return Extremes(most, least, num)

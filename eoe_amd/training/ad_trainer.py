@@ -30,6 +30,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     anomaly scores, normal half and outlier-exposure half (:458-465), after an evaluation those of the nominal and the anomalous test
     scores (:541-546), bucketed on the device (`eoe_score_hist`), kept in `trainer.histograms` and handed to
     `logger.add_histogram` under the reference's tags.  Off by default.
+  * `extremes=k` ranks an evaluation's scores on the device (`eoe_score_extremes`): per label group the k highest and the k lowest
+    test scores with their dataset indices -- false alarms and misses; the reference ranks only OE individuals this way
+    (`Tree.scores_best` / `imsave_best`) and leaves the test scores to a per-sample JSON -- kept in `trainer.extremes`, logged as
+    JSON and, where the source can hand out test images, as one picture.  Off (0) by default.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -43,7 +47,7 @@ import torch
 
 from .. import ops, parallel
 from ..metrics import (ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve,
-                       score_histograms)
+                       score_extremes, score_histograms)
 from ..msm import apply_msms, check_supported
 from ..normalize import GcnNormalize
 from ..optim import FusedAdam
@@ -134,7 +138,7 @@ class ADTrainer(ABC):
                  device: Union[str, torch.device] = "cuda", oe_limit_samples=np.inf, oe_limit_classes=np.inf,
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
-                 previews: bool = False, histograms: bool = False):
+                 previews: bool = False, histograms: bool = False, extremes: int = 0):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -162,7 +166,18 @@ class ADTrainer(ABC):
         under the reference's tags and steps (`ad_trainer.py:458-465, 541-546`): `Training: CLS{cls} SEED{seed} anomaly_scores normal`
         / `... anomalous` at step `ep`, `Eval: (SD{seed}) anomaly_scores cls{cls} nominal` / `... anomalous` at step 0.  A label without
         scores is skipped (the reference's `make_histogram` would raise).  `run` starts with an empty `self.histograms`.  Default off:
-        no launch, no file, the same return values and files as before."""
+        no launch, no file, the same return values and files as before.
+
+        `extremes=k` (k in [1, 1024]): after its metrics `eval_cls` ranks the test scores it holds (`eoe_amd.metrics.score_extremes`:
+        one call for device scores, only 4 k pairs and three counts come back) -- per label group, nominal (label 0) and anomalous
+        (label 1), the k highest and the k lowest scores, equal scores in ascending position, positions mapped to the loader's dataset
+        indices.  The `metrics.Extremes` is kept in `self.extremes[f"eval_cls{cls}_it{seed}"]` and its `as_dict()` logged as
+        `eval_cls{cls}_it{seed}_extremes` through `logger.logjson`.  With an active logger and a source that offers
+        `test_images(rows)` (ResidentImageSource) the picture `eval_cls{cls}-{clsstr}_it{seed}_extremes` follows through
+        `logger.logimg`: one grid row per non-empty list in the order nominal most, nominal least, anomalous most, anomalous least,
+        every row cut to the shortest of them (k, or a smaller group's size), `rowheaders` naming each row with its group's size;
+        other sources get the JSON alone.  `run` starts with an empty `self.extremes`.  Default 0: no launch, no file, the same
+        return values and files as before."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -201,6 +216,10 @@ class ADTrainer(ABC):
         self.curves = None                                  # filled by run() when with_curves
         self.with_histograms = bool(histograms)
         self.histograms = {}                                # tag -> {step: Histogram}, filled by train_cls / eval_cls when with_histograms
+        if isinstance(extremes, bool) or not isinstance(extremes, (int, np.integer)) or not 0 <= extremes <= 1024:
+            raise ValueError(f"extremes must be an integer in [0, 1024] (0: off), not {extremes!r}")
+        self.n_extremes = int(extremes)
+        self.extremes = {}                                  # f"eval_cls{c}_it{seed}" -> Extremes, filled by eval_cls when n_extremes > 0
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -314,6 +333,7 @@ class ADTrainer(ABC):
         eval_rocs, eval_prcs = [[] for _ in range(n_cls)], [[] for _ in range(n_cls)]
         means = {k: [None] * n_cls for k in ("mean_train_rocs", "mean_eval_rocs", "mean_eval_prcs")}
         self.histograms = {}
+        self.extremes = {}
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
@@ -441,6 +461,27 @@ class ADTrainer(ABC):
             if hist is not None:
                 self.histograms.setdefault(tag, {})[step] = hist
                 self.logger.add_histogram(tag, hist, step)
+
+    EXTREME_ROWS = ("nominal most", "nominal least", "anomalous most", "anomalous least")
+
+    def _log_extremes(self, ds, la: torch.Tensor, sc: torch.Tensor, idc: np.ndarray, cls: int, clsstr: str, seed: int):
+        """the k most and least anomalous test samples per label group (`extremes=k` only): kept, logged as JSON and, for a source
+        with `test_images` under an active logger, as a picture of one row per non-empty list"""
+        if sc.numel() == 0:
+            return
+        ex = score_extremes(la, sc, self.n_extremes, indices=idc)
+        self.extremes[f"eval_cls{cls}_it{seed}"] = ex
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_extremes", ex.as_dict())
+        if not (self.logger.active and hasattr(ds, "test_images")):
+            return
+        lists = [(name, pair[0], ex.num[g]) for name, g, pair in zip(self.EXTREME_ROWS, (0, 0, 1, 1),
+                                                                    (ex.most[0], ex.least[0], ex.most[1], ex.least[1])) if len(pair[0])]
+        if not lists:
+            return
+        per = min(len(rows) for _, rows, _ in lists)
+        imgs = ds.test_images(np.concatenate([rows[:per] for _, rows, _ in lists]))
+        self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes", imgs, nrow=per,
+                           rowheaders=[f"{name}: {num}" for name, _, num in lists])
 
     def make_optimizer(self, model: torch.nn.Module):
         """Adam for every encoder (ad_trainer.py:383); the CLIP objective overrides this with SGD-Nesterov (:380-381)"""
@@ -626,6 +667,8 @@ class ADTrainer(ABC):
             self._log_histograms(la_t, sc_t, f"Eval: (SD{seed}) anomaly_scores cls{cls} nominal",
                                  f"Eval: (SD{seed}) anomaly_scores cls{cls} anomalous", 0)
         self.logger.logjson(f"eval_cls{cls}_it{seed}_anomaly_scores", {int(k): float(v) for k, v in zip(idc, sc)})
+        if self.n_extremes > 0:
+            self._log_extremes(ds, la_t, sc_t, idc, cls, clsstr, seed)
         model.cpu()
         return cls_roc, cls_prc
 

@@ -879,6 +879,22 @@ int eoe_rank_curves(const float* scores, const int64_t* labels, int64_t positive
 size_t eoe_score_hist_scratch_bytes(int n);
 int eoe_score_hist(const float* scores, const int64_t* labels, int n, const double* edges_host, const double* edges, int E,
                    int32_t* out_counts, double* out_stats, void* scratch, void* stream);
+/* The extremes of the scores (csrc/topk.hip): per label group the k highest and the k lowest scores and where they stand -- the false
+ * alarms and misses of an evaluation (the reference ranks OE individuals this way, evolve/tree.py scores_best / imsave_best).
+ * Groups as in eoe_score_hist: group 0 = label 0, group 1 = label 1, any other label in neither; labels NULL: every score in group 0.
+ * End 0 ("most") is descending by score, equal scores by ascending position: np.argsort(-s, kind="stable")[:k] over the group's
+ * members; end 1 ("least") ascending by score, equal scores by ascending position: np.argsort(s, kind="stable")[:k].  -0.0 == 0.0.
+ *   scores fp32 [n], labels int64 [n] or NULL; out_idx int32 [2 groups][2 ends][k]: positions in `scores`; out_val fp32 [2][2][k]: the
+ *   selected elements' own bits; out_counts int32 [3]: the sizes m_0, m_1 of the groups and the number of non-finite scores among
+ *   their members.  All DEVICE.  Only the first min(k, m_g) slots of a list are written, the others stay as the caller left them.
+ *   When out_counts[2] != 0 the lists are unspecified (nothing is written out of range).  1 <= n <= 2^20, 1 <= k <= 1024.
+ *   A radix select over distinct 52-bit integer keys (ordered score image, position) and a sort of the at most 1 024 selected keys in
+ *   LDS: integer compares and integer adds only, no n^2 pass, two runs give the same bytes.
+ *   scratch: eoe_score_extremes_scratch_bytes(n, k) bytes (0 for an n or k outside the ranges), 16-byte aligned, may be dirty.  Eight
+ *   enqueues on `stream` (a memset and seven launches); the thresholds stay on the device in between. */
+size_t eoe_score_extremes_scratch_bytes(int n, int k);
+int eoe_score_extremes(const float* scores, const int64_t* labels, int n, int k, int32_t* out_idx, float* out_val, int32_t* out_counts,
+                       void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
