@@ -1182,6 +1182,24 @@ class ResidentImageSource:
             return self._clip_test_batch(idx)[0]
         return self._test_batch(idx)[0]
 
+    def test_inputs(self, rows):
+        """(images, labels, indices) as the test loader yields them for the listed dataset indices, in the listed order (repeats
+        allowed), bit for bit: every row of a test batch is made from its own image alone, so a batch of chosen rows equals those rows
+        of the loader's batches.  What `eoe_amd.explain` differentiates for the rows a ranking picked."""
+        idx = torch.as_tensor(rows).to(torch.int64).cpu().reshape(-1)
+        return self.test_images(idx), self.test_y[idx], idx
+
+    def test_pictures(self, rows):
+        """`test_images(rows)` without the Normalize, whether the batches carry it or not: fp32 NCHW in ToTensor's [0, 1] scale, the
+        pictures `eoe_amd.explain.overlay` lays a map over (it reads fp32 pictures as 255 x).  A source in GCN mode hands out [0, 1]
+        images anyway."""
+        was = getattr(self, "_defer", False)
+        self._defer = True                               # _norm_args() then leaves (mean, std) out; nothing else reads the flag
+        try:
+            return self.test_images(rows)
+        finally:
+            self._defer = was
+
     PREVIEW_SEED = 0x9E3779B1
 
     def preview(self, percls=40, train=True):

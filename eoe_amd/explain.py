@@ -1,0 +1,239 @@
+"""Where in an image does its anomaly score come from: input-gradient heat maps for the LayerNorm (ViT) towers.
+
+  input_gradient(model, images, score_fn)   d score / d image through the training backward (LayerNorm is the same in train and eval
+                                            mode), the last hop -- patch embedding back to pixels -- by `eoe_unpatchify_grad`
+  saliency(grad, x, mode, pool, smooth)     the three-channel gradient reduced to one map per image (`eoe_saliency_map`)
+  overlay(maps, pictures, alpha)            the map laid over the pictures, uint8 NHWC: a form `imgrid.image_grid` takes
+                                            (`eoe_heat_overlay_u8`)
+  score_fn(trainer_or_name, ...)            each objective's `compute_anomaly_score` restated with differentiable torch operations
+  saliency_np / overlay_np                  the numpy statements of the two kernels (tests, CPU tensors)
+
+The BatchNorm encoders (CNN32, CNN28, WideResNet) are not served: their explanation needs an eval-mode BatchNorm backward over the
+running statistics, which no kernel of this package has; `input_gradient` refuses them.
+"""
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib
+
+MODES = {"max": _lib.EOE_SALIENCY_MAX, "l2": _lib.EOE_SALIENCY_L2, "gradxinput": _lib.EOE_SALIENCY_GRADXINPUT}
+HEAT_COLOUR = (255.0, 0.0, 0.0)
+OBJECTIVES = ("hsc", "bce", "focal", "dsad", "dsvdd", "clip")
+
+
+# ------------------------------------------------------------------------------------------------ scores
+def _objective_name(trainer_or_name) -> str:
+    if isinstance(trainer_or_name, str):
+        name = trainer_or_name
+    else:
+        from .training import TRAINER
+        cls = trainer_or_name if isinstance(trainer_or_name, type) else type(trainer_or_name)
+        name = next((k for k, t in TRAINER.items() if issubclass(cls, t)), None)
+    if name not in OBJECTIVES:
+        raise ValueError(f"score_fn: no differentiable score for {trainer_or_name!r}; known objectives: {OBJECTIVES}")
+    return name
+
+
+def score_fn(trainer_or_name, center=None, nominal_label: int = 0):
+    """The differentiable restatement of an objective's `compute_anomaly_score`: a callable features [n, d] -> scores [n] made of torch
+    elementwise operations and row sums (host plumbing on an n x d matrix; the score kernels themselves keep no tape).  `trainer_or_name`
+    is a trainer (its `center` is taken when none is given), a trainer class or one of 'hsc', 'bce', 'focal', 'dsad', 'dsvdd', 'clip';
+    dsvdd needs its centre [1, d], clip the text features [T, d]."""
+    name = _objective_name(trainer_or_name)
+    if center is None and not isinstance(trainer_or_name, (str, type)):
+        center = getattr(trainer_or_name, "center", None)
+    if name in ("dsvdd", "clip") and center is None:
+        raise ValueError(f"score_fn: the {name} score needs its center ({'the text features' if name == 'clip' else 'prepare_metric'})")
+    if name in ("hsc", "dsad"):               # hsc.py:12-15 (dsad.py:12-15 is the same score): 1 - exp(-(sqrt(|f|^2 + 1) - 1))
+        return lambda f: 1 - torch.exp(-(torch.sqrt((f * f).sum(dim=1) + 1) - 1))
+    if name in ("bce", "focal"):              # bce.py:15-17, focal.py:30-32
+        def bce(f):
+            s = torch.sigmoid(f).reshape(f.shape[0])
+            return s if nominal_label == 0 else 1 - s
+        return bce
+    if name == "dsvdd":                       # dsvdd.py:24-25
+        return lambda f: ((f - center.detach().to(f)) ** 2).sum(dim=-1)
+
+    def clip(f):                              # clip.py:66-79: the softmax probability of the last prompt
+        t = center.detach().to(f)
+        t = t / t.norm(dim=-1, keepdim=True)
+        return (100.0 * (f / f.norm(dim=-1, keepdim=True)) @ t.T).softmax(dim=-1)[:, -1]
+    return clip
+
+
+# ------------------------------------------------------------------------------------------------ the gradient
+def input_gradient(model: torch.nn.Module, images: torch.Tensor, score_fn) -> torch.Tensor:
+    """d score_i / d images_i, fp32 of the images' shape [n, 3, H, W], with respect to the tensor handed in (in front of a Normalize the
+    encoder fuses).  `score_fn` maps the model's output [n, d] to [n] scores (`explain.score_fn`).
+
+    One forward with the tape on and one `torch.autograd.grad(seed * score.sum(), images)`: no parameter's `.grad` is touched, and the ViT
+    blocks' backward takes its in-line form (no late write, `ops._late_write_ok`).  The samples of a LayerNorm tower are independent of
+    each other, so the gradient of the sum of the scores IS the per-sample gradient.  That does not hold under BatchNorm, and an
+    eval-mode BatchNorm backward does not exist here: a model with a `_BatchNorm` module is refused.  The model runs in eval mode and
+    gets every module's train / eval flag back afterwards.  `seed` is the package's gradient scale (`eoe_amd.set_grad_scale`: a power of
+    two, 256 for fp16 compute in the trainers, 1 for bf16) times a power of two per image that brings d score_i / d out_i to order one,
+    which keeps the 16-bit dY chain from underflowing even where a score is saturated; `eoe_unpatchify_grad` divides the scale out again
+    and one multiplication of the finished gradient the per-image factors, both exactly."""
+    for m in model.modules():
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+            raise NotImplementedError(f"input_gradient: {type(model).__name__} contains a {type(m).__name__}; an explanation differentiates the "
+                                      "eval-mode BatchNorm (running statistics), whose backward no kernel here implements -- only LayerNorm "
+                                      "(ViT) towers can be explained")
+    flags = [(m, m.training) for m in model.modules()]
+    model.eval()
+    try:
+        x = images.detach().requires_grad_()
+        with torch.enable_grad():
+            out = model(x)
+            # d score / d out on the n x d matrix, in fp32 on its own small tape
+            o = out.detach().requires_grad_()
+            (df,) = torch.autograd.grad(score_fn(o).reshape(-1).sum(), o)
+            # A saturated score (1 - exp(-d) at a large d) has a gradient of 1e-9 and less: behind any fixed seed fp16's dY chain
+            # flushes it.  Each image is therefore seeded with its own power of two, which brings the largest entry of its row into
+            # [1, 2); the factors are exact to apply and to divide out of the finished gradient (eoe_unpatchify_grad undoes the scale).
+            amax = df.abs().amax(dim=1)
+            live = torch.isfinite(amax) & (amax > 0)
+            expo = torch.where(live, torch.floor(torch.log2(torch.where(live, amax, torch.ones_like(amax)))), torch.zeros_like(amax))
+            expo = expo.clamp(-100.0, 100.0)
+            seed = df * (torch.exp2(-expo) * ops.grad_scale())[:, None]
+            (grad,) = torch.autograd.grad(out, x, grad_outputs=seed)
+            grad = grad.mul_(torch.exp2(expo)[:, None, None, None])          # the per-image seeds undone: powers of two, exact
+    finally:
+        for m, was in flags:
+            m.training = was
+    return grad
+
+
+# ------------------------------------------------------------------------------------------------ maps
+def _pool_arg(pool) -> int:
+    pool = 0 if pool is None else int(pool)
+    if pool < 0:
+        raise ValueError(f"saliency: pool must be a positive block size or None, not {pool}")
+    return pool
+
+
+def saliency_np(grad: np.ndarray, x: np.ndarray = None, mode: str = "max", pool=None) -> np.ndarray:
+    """numpy statement of `eoe_saliency_map`: fp32 [n, H, W] from grad [n, C, H, W].  'max' and the products of 'gradxinput' are the
+    kernel's own fp32 operations (exact); sums over channels, the square root and the block means are taken in float64 and rounded once."""
+    g = np.asarray(grad, dtype=np.float32)
+    if mode not in MODES:
+        raise ValueError(f"saliency: mode {mode!r} is none of {tuple(MODES)}")
+    if mode == "max":
+        s = np.fmax.reduce(np.abs(g), axis=1)
+    elif mode == "l2":
+        s = np.sqrt((g.astype(np.float64) ** 2).sum(axis=1))
+    else:
+        if x is None:
+            raise ValueError("saliency: gradxinput needs x")
+        s = np.abs(g * np.asarray(x, dtype=np.float32)).astype(np.float64).sum(axis=1)
+    pool = _pool_arg(pool)
+    if pool > 1:
+        n, H, W = s.shape
+        if H % pool or W % pool:
+            raise ValueError(f"saliency: pool = {pool} does not divide H = {H} and W = {W}")
+        m = s.astype(np.float64).reshape(n, H // pool, pool, W // pool, pool).mean(axis=(2, 4))
+        s = np.repeat(np.repeat(m, pool, axis=1), pool, axis=2)
+    return s.astype(np.float32)
+
+
+def saliency(grad: torch.Tensor, x: torch.Tensor = None, mode: str = "max", pool=None, smooth: float = 0) -> torch.Tensor:
+    """One map per image, fp32 [n, H, W], from a gradient fp32 [n, C, H, W] (C 1 or 3): mode 'max' max_c |g_c|, 'l2' sqrt(sum_c g_c^2),
+    'gradxinput' sum_c |g_c x_c| (needs `x`, the images the gradient belongs to).  `pool=p` gives every aligned p x p block its mean: with
+    p = the patch size, the patch-level map of a ViT.  `smooth=sigma` > 0 blurs the map with the Gaussian of the blur multi-scale mode
+    (`eoe_msm_filter`; taps as `msm.blur_taps_k` / `msm.blur_np`).  One launch on the device (two with smooth); CPU tensors go through
+    `saliency_np` / `msm.blur_np`."""
+    if mode not in MODES:
+        raise ValueError(f"saliency: mode {mode!r} is none of {tuple(MODES)}")
+    if grad.dim() != 4 or grad.shape[1] not in (1, 3):
+        raise ValueError(f"saliency: grad must be [n, C, H, W] with C 1 or 3, not {tuple(grad.shape)}")
+    if mode == "gradxinput" and (x is None or x.shape != grad.shape):
+        raise ValueError("saliency: gradxinput needs x of grad's shape")
+    pool = _pool_arg(pool)
+    n, ch, H, W = grad.shape
+    if pool > 1 and (H % pool or W % pool):
+        raise ValueError(f"saliency: pool = {pool} does not divide H = {H} and W = {W}")
+    if not grad.is_cuda:
+        from .msm import blur_np
+        s = saliency_np(grad.detach().numpy(), None if x is None else x.detach().numpy(), mode, pool)
+        if smooth and smooth > 0:
+            s = blur_np(s[:, None], float(smooth))[:, 0].astype(np.float32)
+        return torch.from_numpy(s)
+    g = grad.detach().contiguous().float()
+    xx = x.detach().to(g.device).contiguous().float() if mode == "gradxinput" else None
+    s = torch.empty((n, H, W), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        check(lib.eoe_saliency_map(g.data_ptr(), ops._p(xx), s.data_ptr(), n, ch, H, W, MODES[mode], pool, ops._stream()), "eoe_saliency_map")
+        if smooth and smooth > 0 and n:
+            from .msm import msm_filter
+            s = msm_filter(s[:, None], "blur", smooth)[:, 0]
+    return s
+
+
+def _pictures_u8(pictures) -> bool:
+    dt = pictures.dtype
+    if dt in (torch.uint8, np.dtype(np.uint8)):
+        return True
+    if dt in (torch.float32, np.dtype(np.float32)):
+        return False
+    raise ValueError(f"overlay: pictures must be fp32 NCHW (ToTensor's scale) or uint8 NHWC, not {dt}")
+
+
+def _overlay_shapes(maps, pictures, alpha):
+    u8 = _pictures_u8(pictures)
+    if maps.ndim != 3 or pictures.ndim != 4:
+        raise ValueError(f"overlay: maps [n, H, W] and pictures of four dimensions, not {tuple(maps.shape)} and {tuple(pictures.shape)}")
+    n, H, W = maps.shape
+    ch = pictures.shape[3] if u8 else pictures.shape[1]
+    want = (n, H, W, ch) if u8 else (n, ch, H, W)
+    if ch not in (1, 3) or tuple(pictures.shape) != want:
+        raise ValueError(f"overlay: {'uint8 NHWC' if u8 else 'fp32 NCHW'} pictures of shape {tuple(pictures.shape)} do not fit maps "
+                         f"{tuple(maps.shape)} (C 1 or 3)")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"overlay: alpha must be in [0, 1], not {alpha}")
+    return u8, n, H, W, ch
+
+
+def overlay_np(maps: np.ndarray, pictures: np.ndarray, alpha: float = 0.6, dtype=np.float32) -> np.ndarray:
+    """numpy statement of `eoe_heat_overlay_u8`, uint8 [n, H, W, 3].  With dtype=np.float32 (the default) every operation is the kernel's,
+    in its order; dtype=np.float64 is the same formula in double precision, which can differ from it only where
+    img (1 - alpha t) + col alpha t + 0.5 lies within rounding of an integer."""
+    maps, pictures = np.asarray(maps, dtype=np.float32), np.asarray(pictures)
+    u8, n, H, W, ch = _overlay_shapes(maps, pictures, alpha)
+    ft = np.dtype(dtype).type
+    img = pictures.astype(dtype) if u8 else (pictures.astype(dtype) * ft(255.0)).transpose(0, 2, 3, 1)
+    img = np.repeat(img, 3, axis=3) if ch == 1 else img
+    out = np.empty((n, H, W, 3), dtype=np.uint8)
+    col = np.array(HEAT_COLOUR, dtype=dtype)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for i in range(n):
+            s = maps[i].astype(dtype)
+            fin = np.isfinite(maps[i])
+            t = np.zeros((H, W), dtype=dtype)
+            if fin.any():
+                lo, hi = s[fin].min(), s[fin].max()
+                d = ft(hi - lo)
+                if d > 0 and np.isfinite(d):
+                    t[fin] = ((s[fin] - lo) / d).astype(dtype)
+            a = (ft(alpha) * t).astype(dtype)[..., None]
+            ia = (ft(1.0) - a).astype(dtype)
+            v = np.floor(((img[i] * ia).astype(dtype) + (col * a).astype(dtype)).astype(dtype) + ft(0.5))
+            out[i] = np.clip(np.nan_to_num(v, nan=0.0), 0.0, 255.0).astype(np.uint8)
+    return out
+
+
+def overlay(maps: torch.Tensor, pictures: torch.Tensor, alpha: float = 0.6) -> torch.Tensor:
+    """The maps fp32 [n, H, W] laid over the pictures -- fp32 NCHW in ToTensor's scale, or uint8 NHWC; one channel fills the three --
+    as uint8 [n, H, W, 3], which `imgrid.image_grid` and `JsonLogger.logimg` take.  Per image t = (s - min) / (max - min) over the map's
+    finite entries (0 for a constant map and at a non-finite entry); byte = floor(img (1 - alpha t) + (255, 0, 0) alpha t + 0.5) with img
+    on the 0...255 scale.  One launch (`eoe_heat_overlay_u8`); CPU tensors go through `overlay_np`."""
+    u8, n, H, W, ch = _overlay_shapes(maps, pictures, alpha)
+    if not maps.is_cuda:
+        return torch.from_numpy(overlay_np(maps.detach().float().numpy(), pictures.detach().cpu().numpy(), alpha))
+    s = maps.detach().contiguous().float()
+    pics = pictures.detach().to(s.device).contiguous()
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=s.device)
+    with torch.cuda.device(s.device):
+        check(lib.eoe_heat_overlay_u8(s.data_ptr(), pics.data_ptr(), 1 if u8 else 0, out.data_ptr(), n, ch, H, W, float(alpha), ops._stream()),
+              "eoe_heat_overlay_u8")
+    return out

@@ -34,6 +34,9 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     test scores with their dataset indices -- false alarms and misses; the reference ranks only OE individuals this way
     (`Tree.scores_best` / `imsave_best`) and leaves the test scores to a per-sample JSON -- kept in `trainer.extremes`, logged as
     JSON and, where the source can hand out test images, as one picture.  Off (0) by default.
+  * `explain=True` (with `extremes`) says where in those images the score comes from: the ViT tower's input gradient through the
+    training backward, reduced to patch-level heat maps and laid over the pictures on the device (`eoe_amd.explain`,
+    csrc/explain.hip), kept in `trainer.explanations` and logged as a second picture.  Off by default; ViT encoders only.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -138,7 +141,7 @@ class ADTrainer(ABC):
                  device: Union[str, torch.device] = "cuda", oe_limit_samples=np.inf, oe_limit_classes=np.inf,
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
-                 previews: bool = False, histograms: bool = False, extremes: int = 0):
+                 previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -177,7 +180,17 @@ class ADTrainer(ABC):
         `logger.logimg`: one grid row per non-empty list in the order nominal most, nominal least, anomalous most, anomalous least,
         every row cut to the shortest of them (k, or a smaller group's size), `rowheaders` naming each row with its group's size;
         other sources get the JSON alone.  `run` starts with an empty `self.extremes`.  Default 0: no launch, no file, the same
-        return values and files as before."""
+        return values and files as before.
+
+        `explain=True` (needs `extremes` > 0, a ViT encoder and a source with `test_inputs(rows)`; anything else raises -- the first
+        here, the other two at the start of `eval_cls`, before any scoring): the rows of the extremes picture are explained
+        (`eoe_amd.explain`).  Their test inputs go through the eval loop's own test-time steps, `input_gradient` differentiates the
+        trainer's score under the gradient scale of the compute type, `saliency(mode="max", pool=patch)` makes the patch-level maps
+        -- kept in `self.explanations[f"eval_cls{cls}_it{seed}"]`, fp32 [rows, H, W] on the device, rows in the picture's order --
+        and `overlay` lays them over `ds.test_pictures(rows)` (those images in the [0, 1] scale, without the source's Normalize); an active logger gets `eval_cls{cls}-{clsstr}_it{seed}_extremes_heat`
+        with the layout and row headers of the extremes picture.  One forward and one backward of the tower over 4 k images at most.
+        The BatchNorm encoders are refused (`explain.input_gradient`).  `run` starts with an empty `self.explanations`.  Default
+        off: no launch, no file, the same return values and files as before."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -220,6 +233,10 @@ class ADTrainer(ABC):
             raise ValueError(f"extremes must be an integer in [0, 1024] (0: off), not {extremes!r}")
         self.n_extremes = int(extremes)
         self.extremes = {}                                  # f"eval_cls{c}_it{seed}" -> Extremes, filled by eval_cls when n_extremes > 0
+        self.with_explain = bool(explain)
+        if self.with_explain and self.n_extremes == 0:
+            raise ValueError("explain=True explains the rows that extremes=k ranks: extremes must be at least 1")
+        self.explanations = {}                              # f"eval_cls{c}_it{seed}" -> fp32 [rows, H, W] maps, filled by eval_cls when with_explain
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -334,6 +351,7 @@ class ADTrainer(ABC):
         means = {k: [None] * n_cls for k in ("mean_train_rocs", "mean_eval_rocs", "mean_eval_prcs")}
         self.histograms = {}
         self.extremes = {}
+        self.explanations = {}
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
@@ -468,20 +486,67 @@ class ADTrainer(ABC):
         """the k most and least anomalous test samples per label group (`extremes=k` only): kept, logged as JSON and, for a source
         with `test_images` under an active logger, as a picture of one row per non-empty list"""
         if sc.numel() == 0:
-            return
+            return None
         ex = score_extremes(la, sc, self.n_extremes, indices=idc)
         self.extremes[f"eval_cls{cls}_it{seed}"] = ex
         self.logger.logjson(f"eval_cls{cls}_it{seed}_extremes", ex.as_dict())
         if not (self.logger.active and hasattr(ds, "test_images")):
-            return
+            return ex
+        rows, per, heads = self._extreme_rows(ex)
+        if per:
+            self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes", ds.test_images(rows), nrow=per, rowheaders=heads)
+        return ex
+
+    def _extreme_rows(self, ex):
+        """the extremes picture's cells: (dataset indices row by row, cells per row, row headers); per = 0 when every list is empty"""
         lists = [(name, pair[0], ex.num[g]) for name, g, pair in zip(self.EXTREME_ROWS, (0, 0, 1, 1),
                                                                     (ex.most[0], ex.least[0], ex.most[1], ex.least[1])) if len(pair[0])]
         if not lists:
-            return
+            return np.zeros(0, np.int64), 0, []
         per = min(len(rows) for _, rows, _ in lists)
-        imgs = ds.test_images(np.concatenate([rows[:per] for _, rows, _ in lists]))
-        self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes", imgs, nrow=per,
-                           rowheaders=[f"{name}: {num}" for name, _, num in lists])
+        return np.concatenate([rows[:per] for _, rows, _ in lists]), per, [f"{name}: {num}" for name, _, num in lists]
+
+    def _test_time_inputs(self, imgs: torch.Tensor, lbls: torch.Tensor, nominal: int) -> torch.Tensor:
+        """the test-time steps between the loader and the encoder (`ad_trainer.py:501-505`): the test MSMs, then GCN"""
+        if self.msms:
+            imgs = apply_msms(imgs, lbls, self.msms, "test", nominal)
+        if self._gcn is not None:
+            imgs = self._gcn(imgs)
+        return imgs
+
+    EXPLAIN_ALPHA = 0.6
+
+    def _check_explainable(self, model, ds):
+        """`explain=True` only: refuse at the start of an evaluation what its end could not explain"""
+        from ..models.clip_vit import VisualTransformer
+        if not hasattr(ds, "test_inputs"):
+            raise NotImplementedError(f"explain=True needs a source with test_inputs(rows); {type(ds).__name__} has none")
+        if not any(isinstance(m, VisualTransformer) for m in model.modules()):
+            raise NotImplementedError(f"explain=True needs a ViT encoder: {type(model).__name__} has no VisualTransformer whose patch "
+                                      "embedding could hand a gradient back to the pixels")
+
+    def _log_explanations(self, model, ds, ex, center, nominal: int, cls: int, clsstr: str, seed: int):
+        """heat maps of the extremes picture's rows (`explain=True` only): kept, and logged as a second picture under an active logger"""
+        from .. import explain
+        from ..models.clip_vit import VisualTransformer
+        rows, per, heads = self._extreme_rows(ex)
+        if not per:
+            return
+        imgs, lbls, _ = ds.test_inputs(rows)
+        imgs = self._test_time_inputs(imgs.to(self.device), lbls, nominal)
+        patch = next(m for m in model.modules() if isinstance(m, VisualTransformer)).patch_size
+        prev_scale = ops.grad_scale()
+        try:
+            ops.set_grad_scale(ops.default_grad_scale())          # as in training: the 16-bit dY chain of fp16 compute must not underflow
+            grad = explain.input_gradient(model, imgs, explain.score_fn(self, center, nominal))
+        finally:
+            ops.set_grad_scale(prev_scale)
+        maps = explain.saliency(grad, mode="max", pool=patch)
+        self.explanations[f"eval_cls{cls}_it{seed}"] = maps
+        if self.logger.active and hasattr(ds, "test_pictures"):
+            # the pictures in ToTensor's scale, which overlay reads as 255 x: test_images(rows) carries the source's Normalize
+            heat = explain.overlay(maps, ds.test_pictures(rows), self.EXPLAIN_ALPHA)
+            self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_heat", heat, nrow=per, rowheaders=heads)
 
     def make_optimizer(self, model: torch.nn.Module):
         """Adam for every encoder (ad_trainer.py:383); the CLIP objective overrides this with SGD-Nesterov (:380-381)"""
@@ -620,6 +685,8 @@ class ADTrainer(ABC):
     def eval_cls(self, model: torch.nn.Module, ds, cls: int, clsstr: str, seed: int):
         """forward-only scoring of the test split, `ad_trainer.py:473-550`"""
         model = model.to(self.device).eval()
+        if self.with_explain:
+            self._check_explainable(model, ds)
         self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
         self._log_preview(ds, f"eval_cls{cls}-{clsstr}_preview", 20, False, seed)                         # :486-493
@@ -632,10 +699,7 @@ class ADTrainer(ABC):
         try:
             for batch in loader:
                 imgs, lbls = batch[0].to(self.device), batch[1]
-                if self.msms:                                                                           # :501-505
-                    imgs = apply_msms(imgs, lbls, self.msms, "test", nominal)
-                if self._gcn is not None:
-                    imgs = self._gcn(imgs)
+                imgs = self._test_time_inputs(imgs, lbls, nominal)                                      # :501-505
                 with torch.no_grad():
                     feats = model(imgs)
                 ep_scores.append(self.compute_anomaly_score(feats, center, inputs=imgs, nominal_label=nominal))
@@ -668,7 +732,9 @@ class ADTrainer(ABC):
                                  f"Eval: (SD{seed}) anomaly_scores cls{cls} anomalous", 0)
         self.logger.logjson(f"eval_cls{cls}_it{seed}_anomaly_scores", {int(k): float(v) for k, v in zip(idc, sc)})
         if self.n_extremes > 0:
-            self._log_extremes(ds, la_t, sc_t, idc, cls, clsstr, seed)
+            ex = self._log_extremes(ds, la_t, sc_t, idc, cls, clsstr, seed)
+            if self.with_explain and ex is not None:
+                self._log_explanations(model, ds, ex, center, nominal, cls, clsstr, seed)
         model.cpu()
         return cls_roc, cls_prc
 

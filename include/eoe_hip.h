@@ -1034,6 +1034,26 @@ int eoe_grid_ragged_u8(const uint8_t* arena, int64_t arena_bytes, const int64_t*
                        int crop_h, int crop_w, const int32_t* table, int n, int groups, int nrow, int pad, int maxres, int sep_height,
                        int sep_at, int marked, float* minmax, uint8_t* out, int64_t out_bytes, void* stream);
 
+/* Explaining a score (csrc/explain.hip): the ViT tower's input gradient, its reduction to one map per image, and the map laid over
+ * the pictures.  All three check their arguments before any launch (EOE_ERR_ARG, naming the argument); n == 0 returns 0 without one.
+ *   eoe_unpatchify_grad  dx fp32 [n, 3, res, res] from dpatches fp32 [n (res / patch)^2, 3 patch^2] (column = c patch^2 + ky patch + kx,
+ *        eoe_patchify's map): dx = dpatches * scale_inv / std[c] (std DEVICE float[3], or NULL: no Normalize was fused).  patch % 4 == 0,
+ *        patch <= 1024,
+ *        res % patch == 0, both buffers 16-byte aligned.  scale_inv a power of two and std NULL: a bit copy of the rearranged values.
+ *   eoe_saliency_map     s fp32 [n, H, W] from g fp32 [n, C, H, W] (C 1 or 3): EOE_SALIENCY_MAX max_c |g_c| (exact), EOE_SALIENCY_L2
+ *        sqrt(sum_c g_c^2), EOE_SALIENCY_GRADXINPUT sum_c |g_c x_c| (x of g's shape; NULL otherwise).  pool > 1: every aligned pool x pool
+ *        block carries the mean of its pixels (pool must divide H and W).  No atomics: the same bytes on every run.
+ *   eoe_heat_overlay_u8  out uint8 [n, H, W, 3] (a form eoe_grid_u8 takes) from s fp32 [n, H, W] and the pictures -- pictures_u8 == 0: fp32
+ *        NCHW in ToTensor's scale (img = 255 x); else uint8 NHWC -- with C 1 or 3 (one channel fills the three).  Per image lo / hi are
+ *        the minimum / maximum of the finite entries of s, t = (s - lo) / (hi - lo), t = 0 where hi == lo, where no entry is finite and
+ *        at a non-finite entry;  byte_c = clamp(floor(img_c (1 - alpha t) + col_c alpha t + 0.5), 0, 255), col = (255, 0, 0), alpha in
+ *        [0, 1]; fp32 operations in this order, no contraction.  One launch, the reduction in a fixed order. */
+enum { EOE_SALIENCY_MAX = 0, EOE_SALIENCY_L2 = 1, EOE_SALIENCY_GRADXINPUT = 2 };
+int eoe_unpatchify_grad(const float* dpatches, const float* std, float scale_inv, float* dx, int n, int res, int patch, void* stream);
+int eoe_saliency_map(const float* g, const float* x, float* s, int n, int C, int H, int W, int mode, int pool, void* stream);
+int eoe_heat_overlay_u8(const float* s, const void* pictures, int pictures_u8, uint8_t* out, int n, int C, int H, int W, float alpha,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
  * its kernel launches with hipEvents on the stream it launches on and records the algorithmic flops / bytes.
