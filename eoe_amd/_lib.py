@@ -19,6 +19,7 @@ EOE_MSM_LPF, EOE_MSM_HPF, EOE_MSM_BLUR = 1, 2, 3
 EOE_MSM_FORM_NONE, EOE_MSM_FORM_DENSE, EOE_MSM_FORM_RANK = 0, 1, 2
 EOE_GCN_L1, EOE_GCN_L2 = 1, 2
 EOE_SALIENCY_MAX, EOE_SALIENCY_L2, EOE_SALIENCY_GRADXINPUT = 0, 1, 2
+EOE_FUSE_MEAN, EOE_FUSE_MAX, EOE_FUSE_MIN = 0, 1, 2
 EOE_COMM_I64, EOE_COMM_ID_BYTES, EOE_COMM_ALGO_RING, EOE_COMM_ALGO_RS_AG = 8, 128, 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD = 0, 1, 2, 3
 # EOE_NT_KERNEL_* (get_option("nt_last_kernel"): the route the last eoe_gemm_nt took; read-only diagnostics)
@@ -273,6 +274,9 @@ SIGNATURES = {
     "eoe_unpatchify_grad": [_vp, _vp, _f32, _vp, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_saliency_map": [_vp, _vp, _vp] + [C.c_int] * 6 + [_vp],
     "eoe_heat_overlay_u8": [_vp, _vp, C.c_int, _vp] + [C.c_int] * 4 + [_f32, _vp],
+    "eoe_attn_probs": [_vp, _vp] + [C.c_int] * 5 + [_vp],
+    "eoe_rollout_step": [_vp, _vp, _vp, C.c_int, C.c_int, _f32, _vp],
+    "eoe_rollout_map": [_vp, _vp] + [C.c_int] * 4 + [_vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
     "eoe_comm_destroy": [_vp],

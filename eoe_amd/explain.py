@@ -8,8 +8,15 @@
   score_fn(trainer_or_name, ...)            each objective's `compute_anomaly_score` restated with differentiable torch operations
   saliency_np / overlay_np                  the numpy statements of the two kernels (tests, CPU tensors)
 
+and, from the forward pass alone, attention rollout (Abnar & Zuidema 2020; csrc/rollout.hip):
+
+  attention_probs(qkv, n, L, heads, fuse)   the softmax probabilities of one block fused over its heads, fp32 [n, L, L] (`eoe_attn_probs`)
+  attention_rollout(model, images, ...)     R <- A^_l R over the blocks in forward order (`eoe_rollout_step`), the class token's row as a
+                                            patch-level map fp32 [n, H, W] (`eoe_rollout_map`): a form `overlay` takes
+  attention_probs_np / attention_rollout_np the float64 numpy statements of the two
+
 The BatchNorm encoders (CNN32, CNN28, WideResNet) are not served: their explanation needs an eval-mode BatchNorm backward over the
-running statistics, which no kernel of this package has; `input_gradient` refuses them.
+running statistics, which no kernel of this package has; `input_gradient` refuses them, and they have no attention to roll out.
 """
 import numpy as np
 import torch
@@ -18,6 +25,7 @@ from . import _lib, ops
 from ._lib import check, lib
 
 MODES = {"max": _lib.EOE_SALIENCY_MAX, "l2": _lib.EOE_SALIENCY_L2, "gradxinput": _lib.EOE_SALIENCY_GRADXINPUT}
+FUSE = {"mean": _lib.EOE_FUSE_MEAN, "max": _lib.EOE_FUSE_MAX, "min": _lib.EOE_FUSE_MIN}
 HEAT_COLOUR = (255.0, 0.0, 0.0)
 OBJECTIVES = ("hsc", "bce", "focal", "dsad", "dsvdd", "clip")
 
@@ -237,3 +245,139 @@ def overlay(maps: torch.Tensor, pictures: torch.Tensor, alpha: float = 0.6) -> t
         check(lib.eoe_heat_overlay_u8(s.data_ptr(), pics.data_ptr(), 1 if u8 else 0, out.data_ptr(), n, ch, H, W, float(alpha), ops._stream()),
               "eoe_heat_overlay_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ attention rollout
+def _fuse_arg(fuse: str) -> int:
+    if fuse not in FUSE:
+        raise ValueError(f"attention: fuse {fuse!r} is none of {tuple(FUSE)}")
+    return FUSE[fuse]
+
+
+def attention_probs_np(qkv: np.ndarray, n: int, L: int, heads: int, fuse: str = "mean") -> np.ndarray:
+    """numpy statement of `eoe_attn_probs` in float64: qkv [n L, 3 D] (the 16-bit values, q | k | v, D = 64 heads) -> [n, L, L].  Per head
+    softmax_rows(q_h k_h^T / 8) with the row maximum subtracted; 'mean' sums the heads in order and multiplies by 1 / heads, 'max' / 'min'
+    take the element-wise extreme."""
+    _fuse_arg(fuse)
+    D = 64 * heads
+    x = np.asarray(qkv, dtype=np.float64).reshape(n, L, 3 * D)
+    out = None
+    for h in range(heads):
+        q, k = x[:, :, 64 * h:64 * h + 64], x[:, :, D + 64 * h:D + 64 * h + 64]
+        s = np.einsum("nqd,nkd->nqk", q, k) / 8.0
+        e = np.exp(s - s.max(axis=2, keepdims=True))
+        p = e / e.sum(axis=2, keepdims=True)
+        out = p if out is None else out + p if fuse == "mean" else np.maximum(out, p) if fuse == "max" else np.minimum(out, p)
+    return out * (1.0 / heads) if fuse == "mean" else out
+
+
+def rollout_matrix_np(probs: np.ndarray, residual: float) -> np.ndarray:
+    """A^ of `eoe_rollout_step` in float64: (1 - residual) probs + residual I, every row divided by its sum; a row whose sum is 0 or not
+    finite is the identity row"""
+    p = np.asarray(probs, dtype=np.float64)
+    eye = np.eye(p.shape[-1])
+    a = (1.0 - residual) * p + residual * eye
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        s = a.sum(axis=-1, keepdims=True)
+        ok = np.isfinite(s) & (s != 0)
+        return np.where(ok, a / np.where(ok, s, 1.0), eye)
+
+
+def attention_rollout_np(probs_per_layer, residual: float, grid: int, patch: int) -> np.ndarray:
+    """numpy statement of the rollout in float64: R = A^_last ... A^_first over the layers' fused probabilities [n, L, L] (forward order),
+    then the class token's row without its class column as [n, grid patch, grid patch], every patch block constant."""
+    if not 0.0 <= residual < 1.0:
+        raise ValueError(f"attention_rollout: residual must be in [0, 1), not {residual}")
+    r = None
+    for p in probs_per_layer:
+        a = rollout_matrix_np(p, residual)
+        r = a if r is None else a @ r
+    n, L, _ = r.shape
+    if L != grid * grid + 1:
+        raise ValueError(f"attention_rollout: L = {L} is not grid^2 + 1 (grid = {grid})")
+    m = r[:, 0, 1:].reshape(n, grid, grid)
+    return np.repeat(np.repeat(m, patch, axis=1), patch, axis=2)
+
+
+def attention_probs(qkv: torch.Tensor, n: int, L: int, heads: int, fuse: str = "mean") -> torch.Tensor:
+    """One block's softmax probabilities fused over its heads, fp32 [n, L, L], from the packed 16-bit qkv [n L, 3 D] the attention kernels
+    read (q | k | v, D = 64 heads; the V third is not read); 1 <= L <= ops.ATTN_LONG_MAX_L.  `fuse`: 'mean' (the heads summed in order,
+    times 1 / heads), 'max', 'min'.  One launch (`eoe_attn_probs`); device tensors only."""
+    code = _fuse_arg(fuse)
+    ops._chk(qkv)
+    if qkv.dim() != 2 or tuple(qkv.shape) != (n * L, 3 * 64 * heads) or not qkv.is_contiguous():
+        raise ValueError(f"attention_probs: qkv must be contiguous [n L, 192 heads] = [{n * L}, {192 * heads}], not {tuple(qkv.shape)}")
+    probs = torch.empty((n, L, L), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        check(lib.eoe_attn_probs(qkv.data_ptr(), probs.data_ptr(), n, L, heads, ops.dtype_code(qkv.dtype), code, ops._stream()), "eoe_attn_probs")
+    return probs
+
+
+def _visual_transformer(model: torch.nn.Module, who: str):
+    from .models.clip_vit import VisualTransformer
+    vit = next((m for m in model.modules() if isinstance(m, VisualTransformer)), None)
+    if vit is None:
+        raise NotImplementedError(f"{who}: {type(model).__name__} has no VisualTransformer whose attention could be rolled out")
+    return vit
+
+
+def block_qkv(blk, tok: torch.Tensor) -> torch.Tensor:
+    """the packed 16-bit qkv [n L, 3 D] of a ResidualAttentionBlock from its input tokens fp32 [n L, D], by the stand-alone operations the
+    block's own kernel chain is made of: LayerNorm-1 into the compute type, the in-projection as an NT GEMM with its bias"""
+    M, D = tok.shape
+    dt = ops.compute_dtype()
+    xn = torch.empty((M, D), dtype=dt, device=tok.device)
+    stats = torch.empty((M, 2), dtype=torch.float32, device=tok.device)
+    ops.layernorm_fwd(tok, blk.ln_1.weight, blk.ln_1.bias, M, D, D, xn, stats)
+    w16, _ = ops.shadow.get(blk.attn.in_proj_weight, True, True)
+    qkv = torch.empty((M, 3 * D), dtype=dt, device=tok.device)
+    return ops.gemm_nt(xn, w16, qkv, bias=blk.attn.in_proj_bias)
+
+
+def attention_rollout(model: torch.nn.Module, images: torch.Tensor, fuse: str = "mean", residual: float = 0.5,
+                      start_layer: int = 0) -> torch.Tensor:
+    """Attention rollout of the model's ViT tower, fp32 [n, H, W] (H = W = the tower's input resolution): how much of each patch reaches
+    the class token through the attention of the blocks `start_layer` ... last, every patch block of a map constant -- a form `overlay`
+    and `imgrid.image_grid` take.
+
+    Forward pass only, under `torch.no_grad()`: the images are embedded as `VisualTransformer.forward` embeds them (the fused Normalize
+    included); per block the packed qkv is computed from the block's input (`block_qkv`), `eoe_attn_probs` fuses the heads' softmax
+    probabilities ('mean', 'max' or 'min'), and `eoe_rollout_step` takes R <- A^ R with A^ = (1 - residual) P + residual I, rows
+    normalised -- the matrix form in forward order, which holds one [n, L, L] probability buffer and two R buffers whatever the depth.
+    `eoe_rollout_map` cuts the class token's row into the map.  `residual` in [0, 1) is the weight of the skip connection (0.5 in the
+    paper); a negative `start_layer` counts from the end.  `start_layer = -1` with `residual = 0` is the raw class-token attention of
+    the last block, bit for bit row 0 of its `attention_probs` (a row whose fp32 sum is one within the sum's own rounding, 2^-20,
+    is not divided again).  Neither the score nor the objective enters: the map does not fade where
+    a score saturates.  A model without a VisualTransformer is refused (NotImplementedError), CPU tensors as the tower refuses them."""
+    code = _fuse_arg(fuse)
+    vit = _visual_transformer(model, "attention_rollout")
+    if not 0.0 <= float(residual) < 1.0:
+        raise ValueError(f"attention_rollout: residual must be in [0, 1), not {residual}")
+    blocks = list(vit.transformer.resblocks)
+    first = int(start_layer) + len(blocks) if start_layer < 0 else int(start_layer)
+    if not 0 <= first < len(blocks):
+        raise ValueError(f"attention_rollout: start_layer {start_layer} outside a tower of {len(blocks)} blocks")
+    if not images.is_cuda:
+        raise RuntimeError("eoe_amd.VisualTransformer runs on the GPU only (no CPU fallback)")
+    n, grid, patch = images.shape[0], vit.input_resolution // vit.patch_size, vit.patch_size
+    L = grid * grid + 1
+    with torch.no_grad(), torch.cuda.device(images.device):
+        tok = vit.embed(images)
+        dev = tok.device
+        probs = torch.empty((n, L, L), dtype=torch.float32, device=dev)
+        r = [torch.empty_like(probs), torch.empty_like(probs)]
+        cur = None                                                 # index of the buffer that holds R; None: the identity
+        for i, blk in enumerate(blocks):
+            if i >= first:
+                qkv = block_qkv(blk, tok)
+                check(lib.eoe_attn_probs(qkv.data_ptr(), probs.data_ptr(), n, L, blk.n_head, ops.dtype_code(qkv.dtype), code, ops._stream()),
+                      "eoe_attn_probs")
+                nxt = 0 if cur is None else 1 - cur
+                check(lib.eoe_rollout_step(probs.data_ptr(), None if cur is None else r[cur].data_ptr(), r[nxt].data_ptr(), n, L,
+                                           float(residual), ops._stream()), "eoe_rollout_step")
+                cur = nxt
+            if i + 1 < len(blocks):
+                tok = blk.forward_tokens(tok, n)
+        maps = torch.empty((n, grid * patch, grid * patch), dtype=torch.float32, device=dev)
+        check(lib.eoe_rollout_map(r[cur].data_ptr(), maps.data_ptr(), n, L, grid, patch, ops._stream()), "eoe_rollout_map")
+    return maps

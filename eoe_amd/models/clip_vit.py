@@ -142,17 +142,22 @@ class VisualTransformer(nn.Module):
             self.normalize = (torch.as_tensor(mean, dtype=torch.float32, device=dev).contiguous(),
                               torch.as_tensor(std, dtype=torch.float32, device=dev).contiguous())
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        """images -> the residual stream entering block 0, fp32 [n L, D] (model.py:220-225): what `forward` starts with, for a caller that
+        walks the blocks itself (`eoe_amd.explain.attention_rollout`)"""
         if not x.is_cuda:
             raise RuntimeError("eoe_amd.VisualTransformer runs on the GPU only (no CPU fallback)")
-        n = x.shape[0]
         mean, std = self.normalize if self.normalize is not None else (None, None)
         # all 16-bit weight copies that the optimiser step made stale, in one launch (48 matrices for 12 blocks)
         ops.shadow.refresh([w for blk in self.transformer.resblocks
                             for w in (blk.attn.in_proj_weight, blk.attn.out_proj.weight, blk.mlp.c_fc.weight, blk.mlp.c_proj.weight)]
                            + [self.proj])
-        tok = ops.VitEmbedFunction.apply(x, self.conv1.weight, self.class_embedding, self.positional_embedding,
-                                         self.ln_pre.weight, self.ln_pre.bias, self.patch_size, mean, std)
+        return ops.VitEmbedFunction.apply(x, self.conv1.weight, self.class_embedding, self.positional_embedding,
+                                          self.ln_pre.weight, self.ln_pre.bias, self.patch_size, mean, std)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        n = x.shape[0]
+        tok = self.embed(x)
         # ln_post reads x[:, 0, :] only (model.py:231-232): the last block is asked for its class-token rows alone -- [n, D], which the
         # head takes as a one-token sequence -- and skips the out-projection, LayerNorm-2 and MLP of the other L - 1 tokens
         blocks = list(self.transformer.resblocks)

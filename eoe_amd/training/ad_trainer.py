@@ -37,6 +37,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
   * `explain=True` (with `extremes`) says where in those images the score comes from: the ViT tower's input gradient through the
     training backward, reduced to patch-level heat maps and laid over the pictures on the device (`eoe_amd.explain`,
     csrc/explain.hip), kept in `trainer.explanations` and logged as a second picture.  Off by default; ViT encoders only.
+  * `attention=True` (with `extremes`) answers the same question from the forward pass alone: the attention rollout of the ViT tower
+    over those images (`eoe_amd.explain.attention_rollout`, csrc/rollout.hip) -- no backward, no dependence on the objective or on a
+    saturated score -- kept in `trainer.attention_maps` and logged as a picture of its own.  Off by default; ViT encoders only;
+    independent of `explain`.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -141,7 +145,8 @@ class ADTrainer(ABC):
                  device: Union[str, torch.device] = "cuda", oe_limit_samples=np.inf, oe_limit_classes=np.inf,
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
-                 previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False):
+                 previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
+                 attention: bool = False):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -190,7 +195,16 @@ class ADTrainer(ABC):
         and `overlay` lays them over `ds.test_pictures(rows)` (those images in the [0, 1] scale, without the source's Normalize); an active logger gets `eval_cls{cls}-{clsstr}_it{seed}_extremes_heat`
         with the layout and row headers of the extremes picture.  One forward and one backward of the tower over 4 k images at most.
         The BatchNorm encoders are refused (`explain.input_gradient`).  `run` starts with an empty `self.explanations`.  Default
-        off: no launch, no file, the same return values and files as before."""
+        off: no launch, no file, the same return values and files as before.
+
+        `attention=True` (the same three conditions, refused the same way): the rows of the extremes picture get their attention
+        rollout (`eoe_amd.explain.attention_rollout`, defaults: the heads' mean, residual 0.5, every block): their test inputs go
+        through the eval loop's own test-time steps and one forward pass of the tower, nothing is differentiated and neither the
+        objective nor the centre enters.  The maps are kept in `self.attention_maps[f"eval_cls{cls}_it{seed}"]`, fp32 [rows, H, W] on
+        the device, rows in the picture's order; an active logger with a source that offers `test_pictures` gets
+        `eval_cls{cls}-{clsstr}_it{seed}_extremes_attn`, laid over the pictures like the heat maps.  `run` starts with an empty
+        `self.attention_maps`.  Independent of `explain`; default off: no launch, no file, the same return values and files as
+        before."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -237,6 +251,10 @@ class ADTrainer(ABC):
         if self.with_explain and self.n_extremes == 0:
             raise ValueError("explain=True explains the rows that extremes=k ranks: extremes must be at least 1")
         self.explanations = {}                              # f"eval_cls{c}_it{seed}" -> fp32 [rows, H, W] maps, filled by eval_cls when with_explain
+        self.with_attention = bool(attention)
+        if self.with_attention and self.n_extremes == 0:
+            raise ValueError("attention=True rolls out the rows that extremes=k ranks: extremes must be at least 1")
+        self.attention_maps = {}                            # the same keys -> fp32 [rows, H, W] rollout maps, filled by eval_cls when with_attention
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -352,6 +370,7 @@ class ADTrainer(ABC):
         self.histograms = {}
         self.extremes = {}
         self.explanations = {}
+        self.attention_maps = {}
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
@@ -516,14 +535,28 @@ class ADTrainer(ABC):
 
     EXPLAIN_ALPHA = 0.6
 
-    def _check_explainable(self, model, ds):
-        """`explain=True` only: refuse at the start of an evaluation what its end could not explain"""
+    def _check_explainable(self, model, ds, option: str = "explain",
+                           why: str = "whose patch embedding could hand a gradient back to the pixels"):
+        """`explain=True` / `attention=True` only: refuse at the start of an evaluation what its end could not explain"""
         from ..models.clip_vit import VisualTransformer
         if not hasattr(ds, "test_inputs"):
-            raise NotImplementedError(f"explain=True needs a source with test_inputs(rows); {type(ds).__name__} has none")
+            raise NotImplementedError(f"{option}=True needs a source with test_inputs(rows); {type(ds).__name__} has none")
         if not any(isinstance(m, VisualTransformer) for m in model.modules()):
-            raise NotImplementedError(f"explain=True needs a ViT encoder: {type(model).__name__} has no VisualTransformer whose patch "
-                                      "embedding could hand a gradient back to the pixels")
+            raise NotImplementedError(f"{option}=True needs a ViT encoder: {type(model).__name__} has no VisualTransformer {why}")
+
+    def _log_attention(self, model, ds, ex, nominal: int, cls: int, clsstr: str, seed: int):
+        """attention-rollout maps of the extremes picture's rows (`attention=True` only): kept, and logged as a picture under an active logger"""
+        from .. import explain
+        rows, per, heads = self._extreme_rows(ex)
+        if not per:
+            return
+        imgs, lbls, _ = ds.test_inputs(rows)
+        imgs = self._test_time_inputs(imgs.to(self.device), lbls, nominal)
+        maps = explain.attention_rollout(model, imgs)
+        self.attention_maps[f"eval_cls{cls}_it{seed}"] = maps
+        if self.logger.active and hasattr(ds, "test_pictures"):
+            attn = explain.overlay(maps, ds.test_pictures(rows), self.EXPLAIN_ALPHA)
+            self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_attn", attn, nrow=per, rowheaders=heads)
 
     def _log_explanations(self, model, ds, ex, center, nominal: int, cls: int, clsstr: str, seed: int):
         """heat maps of the extremes picture's rows (`explain=True` only): kept, and logged as a second picture under an active logger"""
@@ -687,6 +720,8 @@ class ADTrainer(ABC):
         model = model.to(self.device).eval()
         if self.with_explain:
             self._check_explainable(model, ds)
+        if self.with_attention:
+            self._check_explainable(model, ds, "attention", "whose attention could be rolled out")
         self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
         self._log_preview(ds, f"eval_cls{cls}-{clsstr}_preview", 20, False, seed)                         # :486-493
@@ -735,6 +770,8 @@ class ADTrainer(ABC):
             ex = self._log_extremes(ds, la_t, sc_t, idc, cls, clsstr, seed)
             if self.with_explain and ex is not None:
                 self._log_explanations(model, ds, ex, center, nominal, cls, clsstr, seed)
+            if self.with_attention and ex is not None:
+                self._log_attention(model, ds, ex, nominal, cls, clsstr, seed)
         model.cpu()
         return cls_roc, cls_prc
 

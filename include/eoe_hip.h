@@ -1054,6 +1054,25 @@ int eoe_saliency_map(const float* g, const float* x, float* s, int n, int C, int
 int eoe_heat_overlay_u8(const float* s, const void* pictures, int pictures_u8, uint8_t* out, int n, int C, int H, int W, float alpha,
                         void* stream);
 
+/* Attention rollout (csrc/rollout.hip; Abnar & Zuidema 2020): where a ViT tower's class token attends, from the forward pass alone.  All
+ * three check their arguments before any launch (EOE_ERR_ARG: a null pointer, n, L or heads <= 0, L > EOE_ATTN_LONG_MAX_L, an unknown dtype or
+ * fuse code, residual outside [0, 1), r_out overlapping r_in or probs, L != grid^2 + 1), allocate nothing, use no atomics and give the same
+ * bits on every run.
+ *   eoe_attn_probs    probs fp32 [n, L, L] from qkv in eoe_attn_fwd's layout (16-bit [n*L, 3*D], q | k | v, D = heads*64; the V third is never
+ *        read), 1 <= L <= EOE_ATTN_LONG_MAX_L: per head P_h = softmax_rows(q_h k_h^T / 8) -- the products on the matrix cores with fp32
+ *        accumulation, the softmax in fp32 with the row maximum subtracted -- fused over the heads: EOE_FUSE_MEAN the sum over h = 0 ..
+ *        heads - 1 in that order times 1.0f / heads, EOE_FUSE_MAX / EOE_FUSE_MIN the element-wise maximum / minimum.
+ *   eoe_rollout_step  r_out = A^ r_in per image, fp32 [n, L, L] each: A^ = (1 - residual) probs + residual I with every row divided by its own
+ *        fp32 sum (a row whose sum is 0 or not finite is the identity row; a sum within 2^-20 of one -- its own worst-case rounding -- is
+ *        taken as one, so an already normalised row keeps its bits); A^ is formed on the fly.  r_in == NULL is the identity (r_out =
+ *        A^), bit for bit what an explicit identity gives; with residual == 0 and rows that sum to one that is probs itself.
+ *   eoe_rollout_map   maps fp32 [n, grid*patch, grid*patch] from r fp32 [n, L, L], L == grid^2 + 1: pixel (y, x) = r[i, 0, 1 + (y / patch) *
+ *        grid + x / patch] -- the class token's row without the class column, every patch block constant (a form eoe_heat_overlay_u8 takes). */
+enum { EOE_FUSE_MEAN = 0, EOE_FUSE_MAX = 1, EOE_FUSE_MIN = 2 };
+int eoe_attn_probs(const void* qkv, float* probs, int n, int L, int heads, int dtype, int fuse, void* stream);
+int eoe_rollout_step(const float* probs, const float* r_in, float* r_out, int n, int L, float residual, void* stream);
+int eoe_rollout_map(const float* r, float* maps, int n, int L, int grid, int patch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
  * its kernel launches with hipEvents on the stream it launches on and records the algorithmic flops / bytes.
