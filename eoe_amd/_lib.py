@@ -274,6 +274,7 @@ SIGNATURES = {
     "eoe_unpatchify_grad": [_vp, _vp, _f32, _vp, C.c_int, C.c_int, C.c_int, _vp],
     "eoe_saliency_map": [_vp, _vp, _vp] + [C.c_int] * 6 + [_vp],
     "eoe_heat_overlay_u8": [_vp, _vp, C.c_int, _vp] + [C.c_int] * 4 + [_f32, _vp],
+    "eoe_conv_image_dgrad": [_vp, _vp, _vp, _f32, _vp] + [C.c_int] * 10 + [_vp],
     "eoe_attn_probs": [_vp, _vp] + [C.c_int] * 5 + [_vp],
     "eoe_rollout_step": [_vp, _vp, _vp, C.c_int, C.c_int, _f32, _vp],
     "eoe_rollout_map": [_vp, _vp] + [C.c_int] * 4 + [_vp],

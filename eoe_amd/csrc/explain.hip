@@ -220,9 +220,168 @@ __global__ __launch_bounds__(OV_NT) void heat_overlay_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------ first-layer dgrad
+// One workgroup per (image, 16 x 16 tile of dx), one thread per pixel, all CIN channels of it in registers.  The output channels of dy go
+// through LDS CD_CC at a time: the tile's window of dy (every position a tap of the tile reaches, at most 22 x 22) transposed to
+// [channel][position] fp32 -- so the lanes of a wave, which sit side by side in the tile, read side by side -- and the weights of those
+// channels as [channel][tap][4] (CIN == 1: [channel][tap]), one LDS read per tap.  A pixel sums its taps in the fixed order (channel,
+// ky, kx) with fmaf: no atomics, the same bits on every run.  With stride 2 a pixel has taps only at ky = (hi + pad) % 2 + 2 j (and
+// likewise kx): the tap loops step by the stride from that start.
+constexpr int CD_T = 16;                       // tile edge
+constexpr int CD_CC = 16;                      // channels of dy per round
+constexpr int CD_MAXK = 7;                     // largest kernel edge
+constexpr int CD_DT = CD_T + CD_MAXK - 1;      // 22: the widest window (stride 1, 7 x 7)
+// plane stride of the transposed window: >= CD_DT^2 = 484 and = 2 (mod 8), so that the four planes a lane quad writes (4 channels apart, 8
+// positions per 32 lanes) fall on 32 different banks
+constexpr int CD_PS = 490;
+static_assert(CD_PS >= CD_DT * CD_DT && CD_PS % 8 == 2, "plane stride of the dy window");
+
+template <typename T> __device__ __forceinline__ void cd_load4(const T* p, float* o) { unpack4<T>(*reinterpret_cast<const u32x2*>(p), o); }
+template <> __device__ __forceinline__ void cd_load4<float>(const float* p, float* o) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+    o[0] = v[0], o[1] = v[1], o[2] = v[2], o[3] = v[3];
+}
+
+// K, S: kernel edge and stride as compile-time constants (0: the run-time values k_rt, s_rt)
+template <typename T, int CIN, int K, int S>
+__global__ __launch_bounds__(CD_T* CD_T) void conv_image_dgrad_kernel(const T* __restrict__ dy, const float* __restrict__ w,
+                                                                      const float* __restrict__ stdv, float scale_inv, float* __restrict__ dx,
+                                                                      int cout, int Hi, int Wi, int Ho, int Wo, int k_rt, int s_rt, int pad,
+                                                                      int tiles_x) {
+    constexpr int WS = CIN == 1 ? 1 : 4;
+    constexpr int MAXJ = K ? (K + (S ? S : 1) - 1) / (S ? S : 1) : CD_MAXK;
+    __shared__ float dyl[CD_CC * CD_PS];
+    __shared__ __attribute__((aligned(16))) float wl[CD_CC * CD_MAXK * CD_MAXK * WS];
+    const int k = K ? K : k_rt, s = S ? S : s_rt, kk = k * k;
+    const int t = threadIdx.x, ty = t >> 4, tx = t & (CD_T - 1);
+    const int img = blockIdx.x, tyb = (int)blockIdx.y / tiles_x, txb = (int)blockIdx.y - tyb * tiles_x;
+    const int hi0 = tyb * CD_T, wi0 = txb * CD_T;
+    // the window of dy the tile's taps reach: rows ho with hi0 <= ho s - pad + ky < hi0 + CD_T for some ky, clipped to dy
+    const int ra = hi0 + pad - (k - 1), ca = wi0 + pad - (k - 1);
+    const int ho_lo = ra > 0 ? (ra + s - 1) / s : 0, wo_lo = ca > 0 ? (ca + s - 1) / s : 0;
+    const int ho_hi = min(Ho - 1, (min(hi0 + CD_T, Hi) - 1 + pad) / s), wo_hi = min(Wo - 1, (min(wi0 + CD_T, Wi) - 1 + pad) / s);
+    const int th = max(ho_hi - ho_lo + 1, 0), tw = max(wo_hi - wo_lo + 1, 0), npos = th * tw;      // th, tw <= CD_DT
+    const unsigned tw_m = tw ? (65536u + tw - 1) / tw : 0u;      // pos / tw = pos * tw_m >> 16 for pos < 512, tw <= 22
+
+    // the thread's taps: LDS offsets of the rows / columns of dy they read, and of their weights
+    const int hi = hi0 + ty, wi = wi0 + tx;
+    const bool live = hi < Hi && wi < Wi;
+    const int ky0 = (hi + pad) % s, kx0 = (wi + pad) % s;
+    int roff[MAXJ], coff[MAXJ], wyo[MAXJ], wxo[MAXJ];
+    bool rok[MAXJ], cok[MAXJ];
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) {
+        const int ky = ky0 + j * s, kx = kx0 + j * s;
+        const int a = hi + pad - ky, b = wi + pad - kx;          // multiples of s
+        const int ho = a / s, wo = b / s;
+        rok[j] = live && ky < k && a >= 0 && ho < Ho;
+        cok[j] = live && kx < k && b >= 0 && wo < Wo;
+        roff[j] = rok[j] ? (ho - ho_lo) * tw : 0;
+        coff[j] = cok[j] ? wo - wo_lo : 0;
+        wyo[j] = ky < k ? ky * k * WS : 0;
+        wxo[j] = kx < k ? kx * WS : 0;
+    }
+
+    float acc[CIN];
+#pragma unroll
+    for (int c = 0; c < CIN; ++c) acc[c] = 0.f;
+    for (int co0 = 0; co0 < cout; co0 += CD_CC) {
+        const int cc = min(CD_CC, cout - co0);                   // a multiple of 4
+        __syncthreads();                                         // the round before has been read
+        for (int e = t; e < npos * (CD_CC / 4); e += CD_T * CD_T) {
+            const int pos = e >> 2, q = (e & 3) * 4;
+            if (q >= cc) continue;
+            const int r = (int)(((unsigned)pos * tw_m) >> 16), c = pos - r * tw;
+            float v[4];
+            cd_load4<T>(dy + (((size_t)img * Ho + ho_lo + r) * Wo + wo_lo + c) * cout + co0 + q, v);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dyl[(q + i) * CD_PS + pos] = v[i];
+        }
+        const float* wsrc = w + (size_t)co0 * CIN * kk;           // the round's weights: cc * CIN * kk contiguous floats
+        for (int e = t; e < cc * CIN * kk; e += CD_T * CD_T) {
+            const int col = e / (CIN * kk), rem = e - col * (CIN * kk), c = rem / kk, tap = rem - c * kk;
+            wl[(col * kk + tap) * WS + c] = wsrc[e];
+        }
+        __syncthreads();
+        for (int col = 0; col < cc; ++col) {
+            const float* dp = dyl + col * CD_PS;
+            const float* wp = wl + col * kk * WS;
+#pragma unroll
+            for (int jy = 0; jy < MAXJ; ++jy) {
+                if (jy * s >= k) break;                           // the same in every lane
+#pragma unroll
+                for (int jx = 0; jx < MAXJ; ++jx) {
+                    if (jx * s >= k) break;
+                    const float d = (rok[jy] && cok[jx]) ? dp[roff[jy] + coff[jx]] : 0.f;
+                    const float* wt = wp + wyo[jy] + wxo[jx];
+                    if (CIN == 1) {
+                        acc[0] = fmaf(d, wt[0], acc[0]);
+                    } else {
+                        const f32x4 w4 = *reinterpret_cast<const f32x4*>(wt);      // the 4th entry is never written nor used
+#pragma unroll
+                        for (int c = 0; c < CIN; ++c) acc[c] = fmaf(d, w4[c], acc[c]);
+                    }
+                }
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int c = 0; c < CIN; ++c) {
+        const float m = stdv ? scale_inv * (1.0f / stdv[c]) : scale_inv;
+        dx[(((size_t)img * CIN + c) * Hi + hi) * Wi + wi] = acc[c] * m;
+    }
+}
+
 inline bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
+template <typename T>
+void conv_image_dgrad_launch(const void* dy, const float* w, const float* stdv, float scale_inv, float* dx, int n, int cin, int cout, int Hi,
+                             int Wi, int Ho, int Wo, int k, int stride, int pad, hipStream_t st) {
+    const int tiles_x = (Wi + CD_T - 1) / CD_T, tiles_y = (Hi + CD_T - 1) / CD_T;
+    const dim3 grid((unsigned)n, (unsigned)(tiles_x * tiles_y)), block(CD_T * CD_T);
+    const T* d = static_cast<const T*>(dy);
+#define EOE_CD(CIN, K, S) \
+    hipLaunchKernelGGL((conv_image_dgrad_kernel<T, CIN, K, S>), grid, block, 0, st, d, w, stdv, scale_inv, dx, cout, Hi, Wi, Ho, Wo, k, stride, pad, tiles_x)
+    const bool five = k == 5 && stride == 1;                    // CNN32's and CNN28's first layer
+    if (cin == 1) { if (five) EOE_CD(1, 5, 1); else EOE_CD(1, 0, 0); }
+    else { if (five) EOE_CD(3, 5, 1); else EOE_CD(3, 0, 0); }
+#undef EOE_CD
+}
+
 }  // namespace
+
+extern "C" int eoe_conv_image_dgrad(const void* dy, const float* w, const float* stdv, float scale_inv, float* dx, int n, int cin, int cout,
+                                    int Hi, int Wi, int kh, int kw, int stride, int pad, int dtype, void* stream) {
+    EOE_CHECK_ARG(dy && w && dx, "conv_image_dgrad: null dy, w or dx");
+    EOE_CHECK_ARG(n >= 0, "conv_image_dgrad: n must not be negative, not %d", n);
+    EOE_CHECK_ARG(cin == 1 || cin == 3, "conv_image_dgrad: cin must be 1 or 3, not %d", cin);
+    EOE_CHECK_ARG(cout >= 4 && cout % 4 == 0 && cout <= 4096, "conv_image_dgrad: cout %% 4 != 0 or outside [4, 4096] (cout = %d)", cout);
+    EOE_CHECK_ARG(kh == kw && kh >= 1 && kh <= CD_MAXK && kh % 2 == 1, "conv_image_dgrad: the kernel must be square, odd and at most 7, not %d x %d",
+                  kh, kw);
+    EOE_CHECK_ARG(stride == 1 || stride == 2, "conv_image_dgrad: stride must be 1 or 2, not %d", stride);
+    EOE_CHECK_ARG(pad >= 0 && pad < kh, "conv_image_dgrad: pad must be in [0, kh), not %d", pad);
+    EOE_CHECK_ARG(Hi >= 1 && Wi >= 1 && Hi <= 2048 && Wi <= 2048, "conv_image_dgrad: images of %d x %d (at most 2048 x 2048)", Hi, Wi);
+    EOE_CHECK_ARG(Hi + 2 * pad >= kh && Wi + 2 * pad >= kw, "conv_image_dgrad: the padded %d x %d image is smaller than the kernel", Hi, Wi);
+    EOE_CHECK_ARG(dtype == EOE_F16 || dtype == EOE_BF16 || dtype == EOE_F32, "conv_image_dgrad: dtype %d is none of EOE_F16, EOE_BF16, EOE_F32",
+                  dtype);
+    EOE_CHECK_ARG(scale_inv == scale_inv && fabsf(scale_inv) < INFINITY, "conv_image_dgrad: scale_inv must be finite");
+    EOE_CHECK_ARG(aligned(dy, dtype == EOE_F32 ? 16 : 8) && aligned(w, 4) && aligned(dx, 4) && (!stdv || aligned(stdv, 4)),
+                  "conv_image_dgrad: dy must be aligned to four of its elements, w, dx and std to 4 bytes");
+    const int Ho = (Hi + 2 * pad - kh) / stride + 1, Wo = (Wi + 2 * pad - kw) / stride + 1;
+    const long long dy_elems = (long long)n * Ho * Wo * cout, dx_elems = (long long)n * cin * Hi * Wi;
+    EOE_CHECK_ARG(dy_elems < (1ll << 31) && dx_elems < (1ll << 31), "conv_image_dgrad: %lld elements of dy or %lld of dx exceed 32-bit indexing",
+                  dy_elems, dx_elems);
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps("conv_image_dgrad", 2.0 * (double)dy_elems * cin * kh * kw,
+                 (double)dy_elems * (dtype == EOE_F32 ? 4.0 : 2.0) + 4.0 * (double)dx_elems + 4.0 * (double)cout * cin * kh * kw, stream);
+    if (dtype == EOE_F16) conv_image_dgrad_launch<f16_t>(dy, w, stdv, scale_inv, dx, n, cin, cout, Hi, Wi, Ho, Wo, kh, stride, pad, st);
+    else if (dtype == EOE_BF16) conv_image_dgrad_launch<bf16_t>(dy, w, stdv, scale_inv, dx, n, cin, cout, Hi, Wi, Ho, Wo, kh, stride, pad, st);
+    else conv_image_dgrad_launch<float>(dy, w, stdv, scale_inv, dx, n, cin, cout, Hi, Wi, Ho, Wo, kh, stride, pad, st);
+    EOE_CHECK_LAUNCH("conv_image_dgrad");
+    return 0;
+}
 
 extern "C" int eoe_unpatchify_grad(const float* dpatches, const float* stdv, float scale_inv, float* dx, int n, int res, int patch,
                                    void* stream) {

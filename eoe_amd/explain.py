@@ -1,12 +1,16 @@
-"""Where in an image does its anomaly score come from: input-gradient heat maps for the LayerNorm (ViT) towers.
+"""Where in an image does its anomaly score come from: input-gradient heat maps for the LayerNorm (ViT) towers and the BatchNorm CNNs
+(CNN32, CNN28).
 
-  input_gradient(model, images, score_fn)   d score / d image through the training backward (LayerNorm is the same in train and eval
-                                            mode), the last hop -- patch embedding back to pixels -- by `eoe_unpatchify_grad`
+  input_gradient(model, images, score_fn)   d score / d image through the training backward in eval mode (LayerNorm is the same in train
+                                            and eval mode; BatchNorm takes its running statistics, `bn_act_pool_bwd_kernel` without batch
+                                            statistics), the last hop -- patch embedding back to pixels -- by `eoe_unpatchify_grad`, a
+                                            CNN's first convolution back to the image by `eoe_conv_image_dgrad`
   saliency(grad, x, mode, pool, smooth)     the three-channel gradient reduced to one map per image (`eoe_saliency_map`)
   overlay(maps, pictures, alpha)            the map laid over the pictures, uint8 NHWC: a form `imgrid.image_grid` takes
                                             (`eoe_heat_overlay_u8`)
   score_fn(trainer_or_name, ...)            each objective's `compute_anomaly_score` restated with differentiable torch operations
   saliency_np / overlay_np                  the numpy statements of the two kernels (tests, CPU tensors)
+  conv_image_dgrad_np                       the float64 numpy statement of `eoe_conv_image_dgrad`
 
 and, from the forward pass alone, attention rollout (Abnar & Zuidema 2020; csrc/rollout.hip):
 
@@ -15,8 +19,9 @@ and, from the forward pass alone, attention rollout (Abnar & Zuidema 2020; csrc/
                                             patch-level map fp32 [n, H, W] (`eoe_rollout_map`): a form `overlay` takes
   attention_probs_np / attention_rollout_np the float64 numpy statements of the two
 
-The BatchNorm encoders (CNN32, CNN28, WideResNet) are not served: their explanation needs an eval-mode BatchNorm backward over the
-running statistics, which no kernel of this package has; `input_gradient` refuses them, and they have no attention to roll out.
+WideResNet (and anything else with a BatchNorm that is not a CNN32's or CNN28's own) is not served: its residual junctions and CBAM
+gates have no eval-mode backward over the running statistics; `input_gradient` refuses it.  No BatchNorm encoder has attention to
+roll out.
 """
 import numpy as np
 import torch
@@ -71,26 +76,64 @@ def score_fn(trainer_or_name, center=None, nominal_label: int = 0):
 
 
 # ------------------------------------------------------------------------------------------------ the gradient
+def _batchnorm_cnn(model: torch.nn.Module, who: str) -> bool:
+    """whether the model is one of the BatchNorm encoders `who` serves: False without any `_BatchNorm` module, True where every one is a
+    direct child of a CNN32 or CNN28; anything else is refused"""
+    from .models.cnn import CNN28, CNN32
+    served = {id(c) for m in model.modules() if isinstance(m, (CNN32, CNN28)) for c in m.children()}
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    for m in bns:
+        if id(m) not in served:
+            raise NotImplementedError(f"{who}: {type(model).__name__} contains a {type(m).__name__} outside a CNN32 or CNN28; an explanation "
+                                      "differentiates the eval-mode BatchNorm (running statistics), and the residual junctions and CBAM "
+                                      "gates (WideResNet) have no eval-mode backward -- only the ViT towers, CNN32 and CNN28 can be explained")
+    return bool(bns)
+
+
+def conv_image_dgrad_np(dy: np.ndarray, w: np.ndarray, n: int, Hi: int, Wi: int, stride: int, pad: int, std=None,
+                        scale_inv: float = 1.0) -> np.ndarray:
+    """numpy statement of `eoe_conv_image_dgrad` in float64: dy [n Ho Wo, cout] and w [cout, cin, kh, kw] -> dx [n, cin, Hi, Wi],
+    dx[i, c, hi, wi] = (scale_inv / std[c]) sum over (co, ky, kx) of dy[(i, ho, wo), co] w[co, c, ky, kx] with ho stride - pad + ky == hi
+    and wo stride - pad + kx == wi; Ho = (Hi + 2 pad - kh) / stride + 1, likewise Wo; std None = 1."""
+    w = np.asarray(w, dtype=np.float64)
+    cout, cin, kh, kw = w.shape
+    Ho, Wo = (Hi + 2 * pad - kh) // stride + 1, (Wi + 2 * pad - kw) // stride + 1
+    d = np.asarray(dy, dtype=np.float64).reshape(n, Ho, Wo, cout)
+    # the gradient of the padded image, tap by tap; rows / columns past what the last output position reads receive nothing
+    full = np.zeros((n, cin, max(Hi + 2 * pad, (Ho - 1) * stride + kh), max(Wi + 2 * pad, (Wo - 1) * stride + kw)))
+    for ky in range(kh):
+        for kx in range(kw):
+            full[:, :, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride] += np.einsum("nhwo,oc->nchw", d, w[:, :, ky, kx])
+    dx = full[:, :, pad:pad + Hi, pad:pad + Wi]
+    m = np.full(cin, float(scale_inv)) if std is None else float(scale_inv) / np.asarray(std, dtype=np.float64).reshape(cin)
+    return dx * m.reshape(1, cin, 1, 1)
+
+
 def input_gradient(model: torch.nn.Module, images: torch.Tensor, score_fn) -> torch.Tensor:
-    """d score_i / d images_i, fp32 of the images' shape [n, 3, H, W], with respect to the tensor handed in (in front of a Normalize the
-    encoder fuses).  `score_fn` maps the model's output [n, d] to [n] scores (`explain.score_fn`).
+    """d score_i / d images_i, fp32 of the images' shape [n, C, H, W] (C = 3; 1 for CNN28), with respect to the tensor handed in (in front
+    of a Normalize the encoder fuses).  `score_fn` maps the model's output [n, d] to [n] scores (`explain.score_fn`).
 
     One forward with the tape on and one `torch.autograd.grad(seed * score.sum(), images)`: no parameter's `.grad` is touched, and the ViT
     blocks' backward takes its in-line form (no late write, `ops._late_write_ok`).  The samples of a LayerNorm tower are independent of
-    each other, so the gradient of the sum of the scores IS the per-sample gradient.  That does not hold under BatchNorm, and an
-    eval-mode BatchNorm backward does not exist here: a model with a `_BatchNorm` module is refused.  The model runs in eval mode and
-    gets every module's train / eval flag back afterwards.  `seed` is the package's gradient scale (`eoe_amd.set_grad_scale`: a power of
-    two, 256 for fp16 compute in the trainers, 1 for bf16) times a power of two per image that brings d score_i / d out_i to order one,
-    which keeps the 16-bit dY chain from underflowing even where a score is saturated; `eoe_unpatchify_grad` divides the scale out again
-    and one multiplication of the finished gradient the per-image factors, both exactly."""
-    for m in model.modules():
-        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
-            raise NotImplementedError(f"input_gradient: {type(model).__name__} contains a {type(m).__name__}; an explanation differentiates the "
-                                      "eval-mode BatchNorm (running statistics), whose backward no kernel here implements -- only LayerNorm "
-                                      "(ViT) towers can be explained")
+    each other, so the gradient of the sum of the scores IS the per-sample gradient.  Under BatchNorm that holds in eval mode only (the
+    running statistics are constants), which is how the model runs here: a CNN32's or CNN28's BatchNorm units take the eval form of their
+    backward (dy = gamma rstd g), and their parameters do not require a gradient while the tape is recorded, so the backward launches no
+    weight-gradient, column-sum or unpack kernel and writes into no gradient arena; the first convolution hands its gradient back to
+    the image (`eoe_conv_image_dgrad`).  A model with a `_BatchNorm` module that is not a direct child of a CNN32 or CNN28 -- WideResNet,
+    or anything that wraps one -- is refused: the residual junctions and the CBAM gates have no eval-mode backward.  The running buffers
+    are not touched; the model gets every module's train / eval flag (and every parameter its `requires_grad`) back afterwards.
+    `seed` is the package's gradient scale
+    (`eoe_amd.set_grad_scale`: a power of two, 256 for fp16 compute in the trainers, 1 for bf16) times a power of two per image that
+    brings d score_i / d out_i to order one, which keeps the 16-bit dY chain from underflowing even where a score is saturated;
+    `eoe_unpatchify_grad` / `eoe_conv_image_dgrad` divides the scale out again and one multiplication of the finished gradient the
+    per-image factors, both exactly."""
+    cnn = _batchnorm_cnn(model, "input_gradient")
     flags = [(m, m.training) for m in model.modules()]
+    frozen = [p for p in model.parameters() if p.requires_grad] if cnn else []
     model.eval()
     try:
+        for p in frozen:
+            p.requires_grad_(False)
         x = images.detach().requires_grad_()
         with torch.enable_grad():
             out = model(x)
@@ -108,6 +151,8 @@ def input_gradient(model: torch.nn.Module, images: torch.Tensor, score_fn) -> to
             (grad,) = torch.autograd.grad(out, x, grad_outputs=seed)
             grad = grad.mul_(torch.exp2(expo)[:, None, None, None])          # the per-image seeds undone: powers of two, exact
     finally:
+        for p in frozen:
+            p.requires_grad_(True)
         for m, was in flags:
             m.training = was
     return grad

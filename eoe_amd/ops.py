@@ -1329,17 +1329,23 @@ def _bn_act_pool_fwd(y, part, R, bn_w, bn_b, rm, rv, nbt, eps, momentum, s, ycod
     return out, out16, idx, stats
 
 
-def _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, dy_dtype, dy_f32, code, maxpool_code=None):
+def _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, dy_dtype, dy_f32, code, maxpool_code=None, need_affine=(True, True)):
     """Backward of `_bn_act_pool_fwd`: dout (layout of `out`) -> (dy [n*H*W, cout], dgamma, dbeta).
       dy_dtype, dy_f32   dy is the operand of what comes next: the fast path's 16-bit wgrad / dgrad GEMMs (compute dtype, 0), the fp32
                          kernels of parity mode and the fp32 linear layer in front of a BatchNorm1d (float32, 1)
       code               as `ycode` of the forward (EOE_Y16 where the saved y is 16-bit)
-      maxpool_code       if not `code`: eoe_bn_act_maxpool_bwd has no dy_f32 argument, it writes an fp32 dy when its code is EOE_F32"""
+      maxpool_code       if not `code`: eoe_bn_act_maxpool_bwd has no dy_f32 argument, it writes an fp32 dy when its code is EOE_F32
+      need_affine        the pair (dgamma wanted, dbeta wanted).  Neither (an explanation): the kernels take null pointers
+                         for the pair, no gradient target is touched and (None, None) comes back in their place.  One of the two: the
+                         kernels write the pair, so the other goes to a throw-away tensor and comes back as None"""
     n, H, W, C, pool, dev = s.n, s.H, s.W, s.cout, s.pool, y.device
     dout = dout.contiguous().float()
     dy = torch.empty((n * H * W, C), dtype=dy_dtype, device=dev)
-    dg = _grad_target(bn_w) if bn_w is not None else None
-    db = _grad_target(bn_b) if bn_b is not None else None
+    need_g, need_b = need_affine
+    dg = db = None
+    if bn_w is not None and (need_g or need_b):
+        dg = _grad_target(bn_w) if need_g else torch.empty_like(bn_w)
+        db = _grad_target(bn_b) if need_b else torch.empty_like(bn_b)
     red = scratch("bn_red", (BN_SCRATCH * C,), torch.float32, dev)
     if isinstance(pool, tuple):
         check(lib.eoe_bn_act_maxpool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(idx), _p(red), _p(dy), _p(dg), _p(db),
@@ -1349,7 +1355,29 @@ def _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, dy_dtype, dy_f32, code,
         check(lib.eoe_bn_act_pool_bwd(_p(y), _p(stats), _p(bn_w), _p(bn_b), _p(dout), _p(red), _p(dy), dy_f32, _p(dg), _p(db), n, H,
                                       W, C, pool, 1 if s.flat_out else 0, 1 if s.training else 0, 0, s.slope, code, _stream()),
               "eoe_bn_act_pool_bwd")
-    return dy, dg, db
+    return dy, dg if need_g else None, db if need_b else None
+
+
+def conv_image_dgrad(dy, conv_w, n, Hi, Wi, stride, pad, std=None, scale_inv=1.0, out=None):
+    """A first-layer convolution's data gradient, back to the image (eoe_conv_image_dgrad): dy [n*Ho*Wo, cout] -- 16-bit or fp32, as
+    `_bn_act_pool_bwd` leaves it -- times the fp32 parameter conv_w [cout, cin, kh, kw], read as it is, into dx fp32 NCHW
+    [n, cin, Hi, Wi], times scale_inv / std[c] (`std`: the fused Normalize's, None = 1).  cin 1 or 3, cout % 4 == 0, a square odd kernel of
+    at most 7, stride 1 or 2, pad < kh.  One launch; no patch matrix, no atomics, the same bits on every run."""
+    _chk(dy, conv_w, std, out)
+    cout, cin, kh, kw = conv_w.shape
+    Ho, Wo = (Hi + 2 * pad - kh) // stride + 1, (Wi + 2 * pad - kw) // stride + 1
+    if dy.dim() != 2 or tuple(dy.shape) != (n * Ho * Wo, cout) or not dy.is_contiguous():
+        raise ValueError(f"conv_image_dgrad: dy must be contiguous [n Ho Wo, cout] = [{n * Ho * Wo}, {cout}], not {tuple(dy.shape)}")
+    if conv_w.dtype != torch.float32 or (std is not None and (std.dtype != torch.float32 or std.numel() != cin)):
+        raise ValueError("conv_image_dgrad: the weight and std are fp32, std of cin entries")
+    code = _lib.EOE_F32 if dy.dtype == torch.float32 else dtype_code(dy.dtype)
+    dx = torch.empty((n, cin, Hi, Wi), dtype=torch.float32, device=dy.device) if out is None else out
+    if dx.dtype != torch.float32 or tuple(dx.shape) != (n, cin, Hi, Wi) or not dx.is_contiguous():
+        raise ValueError(f"conv_image_dgrad: out must be contiguous fp32 [{n}, {cin}, {Hi}, {Wi}]")
+    w, std = conv_w.detach().contiguous(), None if std is None else std.contiguous()
+    check(lib.eoe_conv_image_dgrad(_p(dy), _p(w), _p(std), float(scale_inv), _p(dx), n, cin, cout,
+                                   Hi, Wi, kh, kw, stride, pad, code, _stream()), "eoe_conv_image_dgrad")
+    return dx
 
 
 def _accumulates(d_pass, s) -> bool:
@@ -1428,31 +1456,39 @@ class ConvBnActPoolParityFunction(torch.autograd.Function):
         s = ctx.shape
         n, H, W, cin, cout, is_image, Hi, Wi, kh, kw, stride, pad = s.n, s.H, s.W, s.cin, s.cout, s.is_image, s.Hi, s.Wi, s.kh, s.kw, s.stride, s.pad
         dev = y.device
-        dy, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, torch.float32, 1, dtype_code(_compute_dtype), maxpool_code=_lib.EOE_F32)
+        # a parameter gradient only where autograd asks for one: every training step asks for all of them, an explanation for none
+        _, need_w, need_cb, need_g, need_b = ctx.needs_input_grad[:5]
+        dy, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, torch.float32, 1, dtype_code(_compute_dtype), maxpool_code=_lib.EOE_F32,
+                                      need_affine=(need_g, need_b))
         geo = _geo(n, Hi, Wi, cin, kh, kw, stride, pad, H, W)
         w = conv_w.contiguous()
-        dw = _grad_target(conv_w)
-        _side_ctx = _conv_wgrad_side_begin(dy, x) if CONV_ASYNC_WGRAD else None      # (see _conv_wgrad_side_begin: under dgrad + the next layer)
-        if ctx.packed:                               # x = the NHWC4 image saved by forward: gradient of the zero-padded [cout, 4, kh, kw] weight
-            geo4 = _geo(n, Hi, Wi, 4, kh, kw, stride, pad, H, W)
-            ws_bytes = int(lib.eoe_conv_f32_wgrad_workspace(geo4, cout))
-            ws = scratch("parity_wgrad_ws", (ws_bytes // 4,), torch.float32, dev)
-            dw4 = scratch("parity_dw4", (cout, 4, kh, kw), torch.float32, dev)
-            check(lib.eoe_conv_f32_wgrad(_p(x), 0, None, None, _p(dy), _p(dw4), geo4, cout, _p(ws), ws_bytes, _stream()), "eoe_conv_f32_wgrad")
-            dw.copy_(dw4[:, :3])
-        else:
-            ws_bytes = int(lib.eoe_conv_f32_wgrad_workspace(geo, cout))
-            ws = scratch("parity_wgrad_ws", (ws_bytes // 4,), torch.float32, dev)
-            check(lib.eoe_conv_f32_wgrad(_p(x), 1 if is_image else 0, _p(mean), _p(std), _p(dy), _p(dw), geo, cout, _p(ws), ws_bytes,
-                                         _stream()), "eoe_conv_f32_wgrad")
-        if _side_ctx is not None:
-            _conv_wgrad_side_end(_side_ctx)
+        dw = None
+        if need_w:
+            dw = _grad_target(conv_w)
+            _side_ctx = _conv_wgrad_side_begin(dy, x) if CONV_ASYNC_WGRAD else None      # (see _conv_wgrad_side_begin: under dgrad + the next layer)
+            if ctx.packed:                             # x = the NHWC4 image saved by forward: gradient of the zero-padded [cout, 4, kh, kw] weight
+                geo4 = _geo(n, Hi, Wi, 4, kh, kw, stride, pad, H, W)
+                ws_bytes = int(lib.eoe_conv_f32_wgrad_workspace(geo4, cout))
+                ws = scratch("parity_wgrad_ws", (ws_bytes // 4,), torch.float32, dev)
+                dw4 = scratch("parity_dw4", (cout, 4, kh, kw), torch.float32, dev)
+                check(lib.eoe_conv_f32_wgrad(_p(x), 0, None, None, _p(dy), _p(dw4), geo4, cout, _p(ws), ws_bytes, _stream()), "eoe_conv_f32_wgrad")
+                dw.copy_(dw4[:, :3])
+            else:
+                ws_bytes = int(lib.eoe_conv_f32_wgrad_workspace(geo, cout))
+                ws = scratch("parity_wgrad_ws", (ws_bytes // 4,), torch.float32, dev)
+                check(lib.eoe_conv_f32_wgrad(_p(x), 1 if is_image else 0, _p(mean), _p(std), _p(dy), _p(dw), geo, cout, _p(ws), ws_bytes,
+                                             _stream()), "eoe_conv_f32_wgrad")
+            if _side_ctx is not None:
+                _conv_wgrad_side_end(_side_ctx)
         dcb = None
-        if conv_b is not None:
+        if conv_b is not None and need_cb:
             dcb = _grad_target(conv_b)
             _f32_colsum(dy, dcb)
         dx = None
-        if ctx.needs_input_grad[0] and not is_image:
+        if ctx.needs_input_grad[0] and is_image:
+            # the hop back to the image (an explanation; training never asks): the fused Normalize's 1 / std and the gradient scale undone
+            dx = conv_image_dgrad(dy, conv_w, n, Hi, Wi, stride, pad, std=std, scale_inv=1.0 / _grad_scale)
+        elif ctx.needs_input_grad[0]:
             acc = _accumulates(d_pass, s)
             dx = d_pass if acc else torch.empty((n, Hi, Wi, cin), dtype=torch.float32, device=dev)
             wkd = _parity_packed(conv_w, "d") if cin % 4 == 0 else None
@@ -1610,6 +1646,7 @@ class ConvBnActPoolFunction(torch.autograd.Function):
                                                   dt16=dt if (cfg.want16 and _implicit_conv) else None, only16=cfg.only16)
         ctx.save_for_backward(operand, y, stats, conv_w, conv_b, bn_w, bn_b, idx)
         ctx.shape, ctx.kp, ctx.implicit, ctx.passthrough = s, kp, implicit, passthrough
+        ctx.std = std if is_image else None          # (a plain tensor, not tracked: the image gradient's 1 / std)
         if out16 is None and not passthrough:
             return out
         ctx.set_materialize_grads(False)       # else autograd zero-fills a gradient for the 16-bit copy every step
@@ -1630,37 +1667,44 @@ class ConvBnActPoolFunction(torch.autograd.Function):
         dev, dt = y.device, operand.dtype
         code = dtype_code(dt)
         M = n * H * W
+        # a parameter gradient only where autograd asks for one: every training step asks for all of them, an explanation for none
+        _, need_w, need_cb, need_g, need_b = ctx.needs_input_grad[:5]
         dy16, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, idx, s, dt, 0,
-                                        code | (_lib.EOE_Y16 if y.dtype != torch.float32 else 0))
-        dw = _grad_target(conv_w)
-        _side_ctx = _conv_wgrad_side_begin(dy16, operand) if CONV_ASYNC_WGRAD else None
-        if implicit == 2:
-            _, Hp, Wp, _ = operand.shape
-            gT = torch.empty(((kh + 1) // 2 * 64, cout), dtype=torch.float32, device=dev)
-            conv_gemm_wgrad(operand, dy16, gT, (n, Hp, Wp, 4, kh, kw, stride, 0, H, W), mode=2)
-            check(lib.eoe_stem_unpack_wgrad(_p(gT), _p(dw), cout, kh, kw, _stream()), "eoe_stem_unpack_wgrad")
-        elif implicit:
-            cg = 8 if implicit == 3 else cin          # channels per tap of the gathered tensor (NHWC8 image: 8)
-            geo_w = (n, Hi, Wi, cg, kh, kw, stride, pad, H, W)
-            if cg == cin and dw.is_contiguous() and not _single_pixel(geo_w):
-                conv_gemm_wgrad(operand, dy16, None, geo_w, dw=dw)            # the reduce kernel writes dw's own layout
+                                        code | (_lib.EOE_Y16 if y.dtype != torch.float32 else 0), need_affine=(need_g, need_b))
+        dw = None
+        if need_w:
+            dw = _grad_target(conv_w)
+            _side_ctx = _conv_wgrad_side_begin(dy16, operand) if CONV_ASYNC_WGRAD else None
+            if implicit == 2:
+                _, Hp, Wp, _ = operand.shape
+                gT = torch.empty(((kh + 1) // 2 * 64, cout), dtype=torch.float32, device=dev)
+                conv_gemm_wgrad(operand, dy16, gT, (n, Hp, Wp, 4, kh, kw, stride, 0, H, W), mode=2)
+                check(lib.eoe_stem_unpack_wgrad(_p(gT), _p(dw), cout, kh, kw, _stream()), "eoe_stem_unpack_wgrad")
+            elif implicit:
+                cg = 8 if implicit == 3 else cin          # channels per tap of the gathered tensor (NHWC8 image: 8)
+                geo_w = (n, Hi, Wi, cg, kh, kw, stride, pad, H, W)
+                if cg == cin and dw.is_contiguous() and not _single_pixel(geo_w):
+                    conv_gemm_wgrad(operand, dy16, None, geo_w, dw=dw)            # the reduce kernel writes dw's own layout
+                else:
+                    gT = torch.empty((kh * kw * cg, cout), dtype=torch.float32, device=dev)
+                    conv_gemm_wgrad(operand, dy16, gT, geo_w)
+                    check(lib.eoe_conv_unpack_wgrad(_p(gT), _p(dw), cout, cin, cg, kh, kw, kh * kw * cg, 1, 0, _stream()),
+                          "eoe_conv_unpack_wgrad")
             else:
-                gT = torch.empty((kh * kw * cg, cout), dtype=torch.float32, device=dev)
-                conv_gemm_wgrad(operand, dy16, gT, geo_w)
-                check(lib.eoe_conv_unpack_wgrad(_p(gT), _p(dw), cout, cin, cg, kh, kw, kh * kw * cg, 1, 0, _stream()),
-                      "eoe_conv_unpack_wgrad")
-        else:
-            g = torch.empty((cout, kp), dtype=torch.float32, device=dev)
-            gemm_tn(dy16, operand, g)
-            check(lib.eoe_conv_unpack_wgrad(_p(g), _p(dw), cout, cin, cin, kh, kw, kp, 0, 0, _stream()), "eoe_conv_unpack_wgrad")
-        if _side_ctx is not None:
-            _conv_wgrad_side_end(_side_ctx)
+                g = torch.empty((cout, kp), dtype=torch.float32, device=dev)
+                gemm_tn(dy16, operand, g)
+                check(lib.eoe_conv_unpack_wgrad(_p(g), _p(dw), cout, cin, cin, kh, kw, kp, 0, 0, _stream()), "eoe_conv_unpack_wgrad")
+            if _side_ctx is not None:
+                _conv_wgrad_side_end(_side_ctx)
         dcb = None
-        if conv_b is not None:
+        if conv_b is not None and need_cb:
             dcb = _grad_target(conv_b)
             colsum(dy16, dcb)
         dx = None
-        if ctx.needs_input_grad[0] and not is_image:
+        if ctx.needs_input_grad[0] and is_image:
+            # the hop back to the image (an explanation; training never asks): the fused Normalize's 1 / std and the gradient scale undone
+            dx = conv_image_dgrad(dy16, conv_w, n, Hi, Wi, stride, pad, std=ctx.std, scale_inv=1.0 / _grad_scale)
+        elif ctx.needs_input_grad[0]:
             _, w16t, w16d = _conv_weight_copies(conv_w)
             acc = _accumulates(d_pass, s)
             if _implicit_conv and stride == 1 and kh == kw and cout % 64 == 0:
@@ -1759,7 +1803,8 @@ class BnActFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         y, stats, bn_w, bn_b = ctx.saved_tensors
-        dy, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, None, ctx.shape, torch.float32, 1, dtype_code(_compute_dtype))
+        dy, dg, db = _bn_act_pool_bwd(y, stats, bn_w, bn_b, dout, None, ctx.shape, torch.float32, 1, dtype_code(_compute_dtype),
+                                      need_affine=(ctx.needs_input_grad[1], ctx.needs_input_grad[2]))
         return dy, dg, db, None, None, None, None
 
 

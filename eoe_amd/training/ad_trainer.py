@@ -36,7 +36,8 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     JSON and, where the source can hand out test images, as one picture.  Off (0) by default.
   * `explain=True` (with `extremes`) says where in those images the score comes from: the ViT tower's input gradient through the
     training backward, reduced to patch-level heat maps and laid over the pictures on the device (`eoe_amd.explain`,
-    csrc/explain.hip), kept in `trainer.explanations` and logged as a second picture.  Off by default; ViT encoders only.
+    csrc/explain.hip), kept in `trainer.explanations` and logged as a second picture.  CNN32 and CNN28 are explained the same way,
+    through their eval-mode BatchNorm backward and `eoe_conv_image_dgrad`, with pixel-level maps.  Off by default; not for WideResNet.
   * `attention=True` (with `extremes`) answers the same question from the forward pass alone: the attention rollout of the ViT tower
     over those images (`eoe_amd.explain.attention_rollout`, csrc/rollout.hip) -- no backward, no dependence on the objective or on a
     saturated score -- kept in `trainer.attention_maps` and logged as a picture of its own.  Off by default; ViT encoders only;
@@ -187,17 +188,18 @@ class ADTrainer(ABC):
         other sources get the JSON alone.  `run` starts with an empty `self.extremes`.  Default 0: no launch, no file, the same
         return values and files as before.
 
-        `explain=True` (needs `extremes` > 0, a ViT encoder and a source with `test_inputs(rows)`; anything else raises -- the first
+        `explain=True` (needs `extremes` > 0, a ViT, CNN32 or CNN28 encoder and a source with `test_inputs(rows)`; anything else raises -- the first
         here, the other two at the start of `eval_cls`, before any scoring): the rows of the extremes picture are explained
         (`eoe_amd.explain`).  Their test inputs go through the eval loop's own test-time steps, `input_gradient` differentiates the
         trainer's score under the gradient scale of the compute type, `saliency(mode="max", pool=patch)` makes the patch-level maps
+        (a CNN32 or CNN28: `pool=None`, pixel-level maps; on a grayscale source the gradient has one channel)
         -- kept in `self.explanations[f"eval_cls{cls}_it{seed}"]`, fp32 [rows, H, W] on the device, rows in the picture's order --
         and `overlay` lays them over `ds.test_pictures(rows)` (those images in the [0, 1] scale, without the source's Normalize); an active logger gets `eval_cls{cls}-{clsstr}_it{seed}_extremes_heat`
         with the layout and row headers of the extremes picture.  One forward and one backward of the tower over 4 k images at most.
-        The BatchNorm encoders are refused (`explain.input_gradient`).  `run` starts with an empty `self.explanations`.  Default
+        WideResNet is refused (`explain.input_gradient`).  `run` starts with an empty `self.explanations`.  Default
         off: no launch, no file, the same return values and files as before.
 
-        `attention=True` (the same three conditions, refused the same way): the rows of the extremes picture get their attention
+        `attention=True` (the same three conditions, but a ViT encoder only; refused the same way): the rows of the extremes picture get their attention
         rollout (`eoe_amd.explain.attention_rollout`, defaults: the heads' mean, residual 0.5, every block): their test inputs go
         through the eval loop's own test-time steps and one forward pass of the tower, nothing is differentiated and neither the
         objective nor the centre enters.  The maps are kept in `self.attention_maps[f"eval_cls{cls}_it{seed}"]`, fp32 [rows, H, W] on
@@ -538,11 +540,17 @@ class ADTrainer(ABC):
     def _check_explainable(self, model, ds, option: str = "explain",
                            why: str = "whose patch embedding could hand a gradient back to the pixels"):
         """`explain=True` / `attention=True` only: refuse at the start of an evaluation what its end could not explain"""
+        from .. import explain
         from ..models.clip_vit import VisualTransformer
         if not hasattr(ds, "test_inputs"):
             raise NotImplementedError(f"{option}=True needs a source with test_inputs(rows); {type(ds).__name__} has none")
-        if not any(isinstance(m, VisualTransformer) for m in model.modules()):
-            raise NotImplementedError(f"{option}=True needs a ViT encoder: {type(model).__name__} has no VisualTransformer {why}")
+        if any(isinstance(m, VisualTransformer) for m in model.modules()):
+            return
+        # the BatchNorm CNNs (CNN32, CNN28) hand an input gradient back through their first convolution; they have no attention
+        if option == "explain" and explain._batchnorm_cnn(model, "explain=True"):
+            return
+        raise NotImplementedError(f"{option}=True needs a ViT encoder{' or a CNN32 / CNN28' if option == 'explain' else ''}: "
+                                  f"{type(model).__name__} has no VisualTransformer {why}")
 
     def _log_attention(self, model, ds, ex, nominal: int, cls: int, clsstr: str, seed: int):
         """attention-rollout maps of the extremes picture's rows (`attention=True` only): kept, and logged as a picture under an active logger"""
@@ -567,7 +575,8 @@ class ADTrainer(ABC):
             return
         imgs, lbls, _ = ds.test_inputs(rows)
         imgs = self._test_time_inputs(imgs.to(self.device), lbls, nominal)
-        patch = next(m for m in model.modules() if isinstance(m, VisualTransformer)).patch_size
+        vit = next((m for m in model.modules() if isinstance(m, VisualTransformer)), None)
+        patch = vit.patch_size if vit is not None else None          # a ViT's maps are patch-level, a CNN's pixel-level
         prev_scale = ops.grad_scale()
         try:
             ops.set_grad_scale(ops.default_grad_scale())          # as in training: the 16-bit dY chain of fp16 compute must not underflow

@@ -1054,6 +1054,19 @@ int eoe_saliency_map(const float* g, const float* x, float* s, int n, int C, int
 int eoe_heat_overlay_u8(const float* s, const void* pictures, int pictures_u8, uint8_t* out, int n, int C, int H, int W, float alpha,
                         void* stream);
 
+/* The last hop of a BatchNorm CNN's input gradient (csrc/explain.hip): a first-layer convolution's data gradient, back to the image.
+ *   dx[i, c, hi, wi] = (scale_inv / std[c]) * sum over (co, ky, kx) of dy[(i, ho, wo), co] * w[co, c, ky, kx]
+ *                      with ho * stride - pad + ky == hi and wo * stride - pad + kx == wi
+ * dy [n Ho Wo, cout] as the BatchNorm backward leaves it, 16-bit or fp32 by `dtype` (EOE_F16 | EOE_BF16 | EOE_F32), aligned to four of
+ * its elements; w the fp32 parameter [cout, cin, kh, kw] as it is; dx fp32 NCHW [n, cin, Hi, Wi]; std DEVICE float[cin] of a fused
+ * Normalize (NULL: none); scale_inv undoes the gradient scale.  Ho = (Hi + 2 pad - kh) / stride + 1, likewise Wo.  Served: cin 1 or 3,
+ * cout % 4 == 0 (at most 4096), kh == kw odd and at most 7, stride 1 or 2, 0 <= pad < kh, images up to 2048 x 2048 and no smaller than the
+ * kernel once padded; anything else is EOE_ERR_ARG before any launch; n == 0 returns 0 without one.  One launch, no patch matrix, no
+ * atomics: every element is an fp32 fmaf chain over (co, ky, kx) in that order on the fp32 weights, the same bits on every run; a pixel
+ * no tap reaches is 0. */
+int eoe_conv_image_dgrad(const void* dy, const float* w, const float* std, float scale_inv, float* dx, int n, int cin, int cout, int Hi,
+                         int Wi, int kh, int kw, int stride, int pad, int dtype, void* stream);
+
 /* Attention rollout (csrc/rollout.hip; Abnar & Zuidema 2020): where a ViT tower's class token attends, from the forward pass alone.  All
  * three check their arguments before any launch (EOE_ERR_ARG: a null pointer, n, L or heads <= 0, L > EOE_ATTN_LONG_MAX_L, an unknown dtype or
  * fuse code, residual outside [0, 1), r_out overlapping r_in or probs, L != grid^2 + 1), allocate nothing, use no atomics and give the same
