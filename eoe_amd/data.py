@@ -876,6 +876,7 @@ class ResidentImageSource:
     `grayscale=True` is refused with a ragged set."""
 
     nominal_label, anomalous_label = 0, 1
+    test_classes = None                # the test rows' original class ids (int64 [n_test]) when the source comes from a LabelledImageSet
 
     def __init__(self, normal_u8, oe_u8, test_u8, test_labels, crop, padding=0, mean=None, std=None, flip_first=True,
                  noise_std=0.001, seed=0, device="cuda", resize=None, test_resize=None, color_jitter=None, interpolation="bilinear",
@@ -1319,6 +1320,7 @@ class LabelledImageSet:
         if self.normalize is not None and ds_statistics is None:
             self._stats.setdefault(key, src.ds_statistics)
         src.normal_classes = tuple(int(c) for c in normal_classes)
+        src.test_classes = self.test_classes          # what ad_targets collapsed to 0 / 1 (metrics.class_breakdown)
         if oe_subset is not None:
             src.set_oe_subset(oe_subset)
         return src

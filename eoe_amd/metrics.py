@@ -12,7 +12,11 @@ arrays -- and the same trimming of the integer arrays on the host.
 
 Which test images those numbers rest on -- per label group the highest and the lowest scores with their positions, as the reference
 ranks OE individuals in `Tree.scores_best` -- is `score_extremes`: `eoe_score_extremes` (an exact radix select) for GPU tensors, two
-stable argsorts for host arrays."""
+stable argsorts for host arrays.
+
+Which class causes the misses -- per class of the test split the AUC, the FPR at a TPR level and the AP of that class against the
+pool of all samples of the other side, which the reference does not have -- is `class_breakdown`: `eoe_class_breakdown` (exact
+integer pair counts, one workgroup per class) for GPU tensors, sorts for host arrays."""
 from typing import Optional
 
 import numpy as np
@@ -567,3 +571,220 @@ def score_extremes(labels, scores, k: int = 20, indices=None) -> Extremes:
     if remap is not None:
         most, least = [(remap[i], v) for i, v in most], [(remap[i], v) for i, v in least]
     return Extremes(most, least, num)
+
+
+# ------------------------------------------------------------------------------------------------------ per-class breakdown
+BREAKDOWN_MAX_N = 1 << 20         # eoe_class_breakdown: the cap of eoe_rank_curves
+BREAKDOWN_MAX_CLASSES = 1024      # a dense class id shares one word with the side
+_BD_COLS = 4                      # a row of the integer table: 2U, fps, tps, n_k
+
+
+class Breakdown:
+    """An evaluation's scores broken down by class.  A sample's side is 0 (nominal) when its class is a normal class and 1
+    (anomalous) otherwise; the sub-problem of class k is class k against the pool of ALL samples of the other side, label 1 on the
+    anomalous side.  Arrays have one entry per class present, in ascending order of the class id:
+
+      classes   the class ids (int64);  names  their names (str);  side  0 / 1;  n  the class sizes
+      auc       `roc_auc_score` of the sub-problem: 2U / (2 n_pos n_neg), 2U = sum over (positive, negative) of 2 [s_p > s_n] + [s_p == s_n]
+      fpr       the sub-problem's false-positive rate at the first ROC point whose TPR reaches `tpr_level`
+      ap        `average_precision_score` of the sub-problem for an ANOMALOUS class, a list of floats; None for a nominal class: its
+                positives are the pool, so it would take a count per (pool sample, class), which is not built
+      fpr_at_tpr, threshold   the same rate on the pooled problem (every anomalous sample against every nominal one) and the score
+                at which it is taken: a sample is flagged when its score is >= threshold
+    A class whose pool is empty has NaN in `auc`, `fpr` and `ap`; the pooled numbers are NaN when a side is missing.
+
+    What the rates are divided from is kept as well: `counts` int64 [K + 1, 4] with rows {2U, fps, tps, n} (fps / tps: negatives /
+    positives at or above the threshold; row K: the pooled problem's fps and tps) and `thresholds` [K + 1] in the scores' precision
+    (a nominal class's threshold is the pooled one, its positives being the whole anomalous side); rows of an empty problem are 0 / NaN."""
+
+    def __init__(self, classes, names, side, n, auc, ap, fpr, tpr_level, fpr_at_tpr, threshold, counts=None, thresholds=None):
+        self.classes, self.side, self.n = (np.asarray(a, dtype=np.int64) for a in (classes, side, n))
+        self.names = [str(x) for x in names]
+        self.auc, self.fpr = np.asarray(auc, dtype=np.float64), np.asarray(fpr, dtype=np.float64)
+        self.ap = [None if a is None else float(a) for a in ap]
+        self.tpr_level, self.fpr_at_tpr, self.threshold = float(tpr_level), float(fpr_at_tpr), float(threshold)
+        self.counts = None if counts is None else np.asarray(counts, dtype=np.int64)
+        self.thresholds = None if thresholds is None else np.asarray(thresholds)
+
+    def hardest(self):
+        """(class id, name, auc) of the class with the lowest AUC; None when no class has one"""
+        if not np.isfinite(self.auc).any():
+            return None
+        k = int(np.nanargmin(self.auc))
+        return int(self.classes[k]), self.names[k], float(self.auc[k])
+
+    def to_json(self) -> dict:
+        """ints, floats, strings and None (for NaN and for the AP of a nominal class): strict JSON"""
+        num = lambda x: None if (x is None or x != x) else float(x)                                 # noqa: E731
+        return {"classes": [int(c) for c in self.classes], "names": list(self.names), "side": [int(x) for x in self.side],
+                "n": [int(x) for x in self.n], "auc": [num(x) for x in self.auc], "ap": [num(x) for x in self.ap],
+                "fpr": [num(x) for x in self.fpr], "tpr_level": self.tpr_level, "fpr_at_tpr": num(self.fpr_at_tpr),
+                "threshold": num(self.threshold)}
+
+    def __repr__(self):
+        return f"Breakdown({len(self.classes)} classes, tpr_level={self.tpr_level}, fpr_at_tpr={self.fpr_at_tpr})"
+
+
+def place_for_tpr(tpr: float, n_pos: int) -> int:
+    """the smallest integer m with m / n_pos >= tpr in float64 -- the number of positives the first ROC point with TPR >= tpr holds
+    (sklearn's `tps / tps[-1]` is this division); 0 when there are no positives"""
+    if n_pos < 1:
+        return 0
+    m = min(max(int(np.ceil(tpr * n_pos)), 1), n_pos)
+    while m > 1 and (m - 1) / n_pos >= tpr:
+        m -= 1
+    while m < n_pos and m / n_pos < tpr:
+        m += 1
+    return m
+
+
+def _ge(sorted_x: np.ndarray, q) -> np.ndarray:
+    return sorted_x.size - np.searchsorted(sorted_x, q, side="left")
+
+
+def _gt(sorted_x: np.ndarray, q) -> np.ndarray:
+    return sorted_x.size - np.searchsorted(sorted_x, q, side="right")
+
+
+def _threshold_host(pos: np.ndarray, m: int):
+    """the score at place m (1-based) of `pos` in descending order, with the bits of the smallest index among its equal scores: what
+    a reversed stable sort leaves last in the group (-0.0 and 0.0 are one group)"""
+    v = pos[np.argsort(pos, kind="stable")[::-1][m - 1]]
+    return pos[np.flatnonzero(pos == v)[0]]
+
+
+def _breakdown_host(s: np.ndarray, dense: np.ndarray, side: np.ndarray, m_cls: np.ndarray, m_pooled: int):
+    """the tables of `eoe_class_breakdown` from sorts: (counts int64 [K + 1, 4], ap float64 [K], thresholds [K + 1])"""
+    K = side.size
+    counts, ap, thr = np.zeros((K + 1, _BD_COLS), np.int64), np.zeros(K, np.float64), np.zeros(K + 1, s.dtype)
+    on_side = side[dense]
+    pooled = [s[on_side == 0], s[on_side == 1]]                                  # in index order
+    pool = [np.sort(p) for p in pooled]
+    if m_pooled >= 1:
+        thr[K] = _threshold_host(pooled[1], m_pooled)
+        counts[K, 1], counts[K, 2] = _ge(pool[0], thr[K]), _ge(pool[1], thr[K])
+    by_class = np.argsort(dense, kind="stable")                                  # members of a class in index order
+    starts = np.searchsorted(dense[by_class], np.arange(K + 1))
+    for k in range(K):
+        sk = s[by_class[starts[k]:starts[k + 1]]]
+        counts[k, 3] = sk.size
+        if sk.size == 0:
+            continue
+        if side[k]:
+            ge_pool, ge_own = _ge(pool[0], sk), _ge(np.sort(sk), sk)
+            counts[k, 0] = 2 * sk.size * pool[0].size - int((ge_pool + _gt(pool[0], sk)).sum())
+            ap[k] = float(np.sum(ge_own / (ge_own + ge_pool).astype(np.float64))) / sk.size
+            if m_cls[k] >= 1:
+                thr[k] = _threshold_host(sk, int(m_cls[k]))
+                counts[k, 1], counts[k, 2] = _ge(pool[0], thr[k]), _ge(np.sort(sk), thr[k])
+        else:
+            counts[k, 0] = int((_ge(pool[1], sk) + _gt(pool[1], sk)).sum())
+            counts[k, 1], counts[k, 2], thr[k] = int((sk >= thr[K]).sum()), counts[K, 2], thr[K]
+    return counts, ap, thr
+
+
+def class_breakdown_device(scores, dense, side, m_cls, m_pooled: int):
+    """`eoe_class_breakdown` on GPU-resident scores: (counts int64 [K + 1, 4], ap float64 [K], thresholds float32 [K + 1]) as host
+    arrays.  `dense` int32 [n] (class ids in [0, K)), `side` uint8 [K] and `m_cls` int32 [K] are host arrays: one upload, one call (two
+    memsets and two launches) and ONE copy back."""
+    import torch
+    from ._lib import check, lib
+    if not _is_gpu_tensor(scores):
+        raise RuntimeError("class_breakdown_device needs GPU scores (class_breakdown takes host arrays as they are)")
+    sc = scores.detach().reshape(-1).contiguous().float()
+    n, K = sc.numel(), int(side.size)
+    if n < 1 or n > BREAKDOWN_MAX_N:
+        raise ValueError(f"eoe_class_breakdown takes between 1 and {BREAKDOWN_MAX_N} scores, not {n}")
+    if dense.size != n or m_cls.size != K:
+        raise ValueError(f"one class id per score and one place per class: {dense.size} ids for {n} scores, {m_cls.size} places for {K} classes")
+    # one upload: the class ids, the places and the sides (a byte each, behind the 4-byte words)
+    host = np.concatenate([np.ascontiguousarray(dense, np.int32).view(np.uint8), np.ascontiguousarray(m_cls, np.int32).view(np.uint8),
+                           np.ascontiguousarray(side, np.uint8)])
+    dev = torch.from_numpy(host).to(sc.device)
+    # one buffer, one copy back: the integer table and the APs (8-byte words) first, then the thresholds
+    o_ap, o_thr = (K + 1) * _BD_COLS * 8, (K + 1) * _BD_COLS * 8 + K * 8
+    out = torch.empty(o_thr + (K + 1) * 4, dtype=torch.uint8, device=sc.device)
+    scratch = torch.empty(lib.eoe_class_breakdown_scratch_bytes(n, K), dtype=torch.uint8, device=sc.device)
+    with torch.cuda.device(sc.device):
+        check(lib.eoe_class_breakdown(sc.data_ptr(), dev.data_ptr(), dev.data_ptr() + 4 * n + 4 * K, dev.data_ptr() + 4 * n, int(m_pooled),
+                                      n, K, out.data_ptr(), out.data_ptr() + o_ap, out.data_ptr() + o_thr, scratch.data_ptr(),
+                                      torch.cuda.current_stream(sc.device).cuda_stream), "eoe_class_breakdown")
+    raw = out.cpu().numpy()
+    return (raw[:o_ap].view(np.int64).reshape(K + 1, _BD_COLS).copy(), raw[o_ap:o_thr].view(np.float64).copy(),
+            raw[o_thr:].view(np.float32).copy())
+
+
+def class_breakdown(scores, classes, normal_classes, tpr: float = 0.95, names=None) -> Breakdown:
+    """Which class causes the misses: per class present in `classes` the AUC, the FPR at the first ROC point whose TPR reaches `tpr`
+    and (anomalous classes) the AP of that class against the pool of all samples of the other side, plus the pooled FPR at that TPR
+    and its threshold -- see `Breakdown`.  `classes` holds one class id per score (any integers, a host array or a tensor on either
+    device); a class is nominal iff it is in `normal_classes` (`data.ad_targets`).  `names`: a sequence indexed by class id or a
+    mapping id -> name; ids it does not cover are named by their number.
+
+    FPR at a TPR level: with m the smallest integer with m / n_pos >= tpr (float64, as sklearn's `tps / tps[-1]`), the threshold is
+    the score of the positive whose group of equal scores holds place m among the positives in descending order, and the rate is the
+    share of negatives at or above it: `fpr[np.argmax(tpr_arr >= tpr)]` of `roc_curve(y, s, drop_intermediate=False)`.  For a nominal
+    class the positives are the whole anomalous side, so every nominal class shares the pooled threshold.
+
+    AP is reported for anomalous classes only (None for a nominal class): with the pool as positives it would need a count per (pool
+    sample, class), which is not built.
+
+    GPU scores go through `eoe_class_breakdown` (exact integer pair counts; the class ids are mapped to 0..K-1 on the host, which
+    costs one copy of `classes` when they live on the device, and only the (K + 1) x 4 integers, K APs and K + 1 thresholds come
+    back); host arrays and CPU tensors through sorts.  Both give the same integers and the same threshold bits; the APs agree to the
+    rounding of a float64 sum of n_k terms.  Scores are taken as float32 on the device; host float32 stays float32, anything else is
+    compared as float64.
+
+    ValueError for non-finite scores, no scores, another number of class ids than scores, `tpr` outside (0, 1] and more than 1024
+    classes; the device path takes at most 2^20 scores."""
+    if isinstance(tpr, bool) or not isinstance(tpr, (int, float, np.integer, np.floating)) or not 0.0 < float(tpr) <= 1.0:
+        raise ValueError(f"tpr must be in (0, 1], not {tpr!r}")
+    tpr = float(tpr)
+    ids = np.asarray(_to_host(classes)).ravel()
+    n = int(scores.numel()) if hasattr(scores, "numel") else int(np.asarray(scores).size)
+    if ids.size != n or n == 0:
+        raise ValueError(f"a breakdown needs as many class ids as scores and at least one, not {ids.size} and {n}")
+    if ids.dtype.kind not in "iu":
+        raise ValueError(f"class ids must be integers, not {ids.dtype}")
+    present, dense = np.unique(ids.astype(np.int64), return_inverse=True)
+    K = int(present.size)
+    if K > BREAKDOWN_MAX_CLASSES:
+        raise ValueError(f"a breakdown takes at most {BREAKDOWN_MAX_CLASSES} classes, not {K}")
+    normal = {int(c) for c in np.asarray(_to_host(normal_classes)).ravel()}
+    side = np.array([0 if int(c) in normal else 1 for c in present], dtype=np.uint8)
+    sizes = np.bincount(dense, minlength=K).astype(np.int64)
+    n_side = [int(sizes[side == 0].sum()), int(sizes[side == 1].sum())]
+    m_pooled = place_for_tpr(tpr, n_side[1])
+    m_cls = np.array([place_for_tpr(tpr, int(sizes[k])) if side[k] else m_pooled for k in range(K)], dtype=np.int32)
+    if _is_gpu_tensor(scores):
+        import torch
+        if not bool(torch.isfinite(scores).all()):
+            raise ValueError("scores contain NaN or infinity")
+        counts, ap, thr = class_breakdown_device(scores, dense.astype(np.int32), side, m_cls, m_pooled)
+    else:
+        s = np.asarray(_to_host(scores)).ravel()
+        if s.dtype != np.float32:
+            s = s.astype(np.float64)
+        if not np.isfinite(s).all():
+            raise ValueError("scores contain NaN or infinity")
+        counts, ap, thr = _breakdown_host(s, dense, side, m_cls, m_pooled)
+    # the divisions, once, in float64; a problem with an empty side is cleared to 0 / NaN on both paths
+    auc, fpr, aps = np.full(K, np.nan), np.full(K, np.nan), []
+    for k in range(K):
+        n_pos, n_neg = (int(sizes[k]), n_side[0]) if side[k] else (n_side[1], int(sizes[k]))
+        if n_pos == 0 or n_neg == 0:
+            counts[k, :3], thr[k] = 0, np.nan
+            aps.append(float("nan") if side[k] else None)
+            continue
+        auc[k] = int(counts[k, 0]) / (2 * n_pos * n_neg)
+        fpr[k] = int(counts[k, 1]) / n_neg
+        aps.append(float(ap[k]) if side[k] else None)
+    fpr_at_tpr = float("nan")
+    if n_side[0] and n_side[1]:
+        fpr_at_tpr = int(counts[K, 1]) / n_side[0]
+    else:
+        counts[K, :3], thr[K] = 0, np.nan
+    if names is None:
+        names = {}
+    label = (lambda c: names.get(c, c)) if hasattr(names, "get") else (lambda c: names[c] if 0 <= c < len(names) else c)
+    return Breakdown(present, [label(int(c)) for c in present], side, sizes, auc, aps, fpr, tpr, fpr_at_tpr, float(thr[K]), counts, thr)

@@ -42,6 +42,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     over those images (`eoe_amd.explain.attention_rollout`, csrc/rollout.hip) -- no backward, no dependence on the objective or on a
     saturated score -- kept in `trainer.attention_maps` and logged as a picture of its own.  Off by default; ViT encoders only;
     independent of `explain`.
+  * `breakdown=True` says which class causes the misses: per class of the test split the AUC, the FPR at `breakdown_tpr` and the AP
+    of that class against the pool of all samples of the other side, counted on the device (`eoe_class_breakdown`,
+    csrc/breakdown.hip), kept in `trainer.breakdowns`, logged as JSON, and after `run` as the task x class AUC matrix
+    (`breakdown_matrix()`).  The reference has nothing of the kind.  Off by default; needs a source that kept its test classes.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -55,7 +59,7 @@ import torch
 
 from .. import ops, parallel
 from ..metrics import (ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve,
-                       score_extremes, score_histograms)
+                       score_extremes, score_histograms, class_breakdown)
 from ..msm import apply_msms, check_supported
 from ..normalize import GcnNormalize
 from ..optim import FusedAdam
@@ -147,7 +151,7 @@ class ADTrainer(ABC):
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
                  previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
-                 attention: bool = False):
+                 attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -206,7 +210,19 @@ class ADTrainer(ABC):
         the device, rows in the picture's order; an active logger with a source that offers `test_pictures` gets
         `eval_cls{cls}-{clsstr}_it{seed}_extremes_attn`, laid over the pictures like the heat maps.  `run` starts with an empty
         `self.attention_maps`.  Independent of `explain`; default off: no launch, no file, the same return values and files as
-        before."""
+        before.
+
+        `breakdown=True` (needs a source with `test_classes`, the test rows' original class ids -- a `LabelledImageSet`'s sources have
+        them; anything else raises at the start of `eval_cls`, before any scoring): after its metrics `eval_cls` breaks the test
+        scores down by class (`eoe_amd.metrics.class_breakdown`: one call for device scores) -- per class the AUC, the FPR at the
+        first ROC point whose TPR reaches `breakdown_tpr` and, for anomalous classes, the AP of that class against the pool of all
+        samples of the other side, plus the pooled FPR at that TPR.  Under `one_vs_rest` that splits the anomalies ("cat against
+        dog", "cat against truck"), under `leave_one_out` the nominal side (which class raises the false alarms).  The
+        `metrics.Breakdown` is appended to `self.breakdowns[cls]` (one per seed), its `to_json()` logged as
+        `eval_cls{cls}_it{seed}_breakdown`, and one text line names the hardest class (lowest AUC).  After `run`,
+        `breakdown_matrix()` is the [task, class] matrix of the seeds' mean AUCs, logged with the tasks' mean pooled FPRs as
+        `breakdown_auc`.  `run` starts with an empty `self.breakdowns`.  Default off: no launch, no file, the same return values
+        and files as before."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -257,6 +273,11 @@ class ADTrainer(ABC):
         if self.with_attention and self.n_extremes == 0:
             raise ValueError("attention=True rolls out the rows that extremes=k ranks: extremes must be at least 1")
         self.attention_maps = {}                            # the same keys -> fp32 [rows, H, W] rollout maps, filled by eval_cls when with_attention
+        self.with_breakdown = bool(breakdown)
+        if isinstance(breakdown_tpr, bool) or not isinstance(breakdown_tpr, (int, float)) or not 0.0 < breakdown_tpr <= 1.0:
+            raise ValueError(f"breakdown_tpr must be in (0, 1], not {breakdown_tpr!r}")
+        self.breakdown_tpr = float(breakdown_tpr)
+        self.breakdowns = {}                                # cls -> [Breakdown per seed], filled by eval_cls when with_breakdown
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -373,6 +394,7 @@ class ADTrainer(ABC):
         self.extremes = {}
         self.explanations = {}
         self.attention_maps = {}
+        self.breakdowns = {}
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
@@ -421,6 +443,12 @@ class ADTrainer(ABC):
         self.logger.logjson("results", {"eval_mean_auc": mean_auc, "eval_std_auc": std_auc,
                                         "eval_mean_avg_prec": mean_avg_prec, "eval_cls_rocs": cls_aucs,
                                         "classes": self.classes})
+        if self.with_breakdown and self.breakdowns:
+            nan_none = lambda x: None if x != x else float(x)                                       # noqa: E731
+            self.logger.logjson("breakdown_auc", {
+                "auc": [[nan_none(x) for x in row] for row in self.breakdown_matrix()], "tpr_level": self.breakdown_tpr,
+                "fpr_at_tpr": [nan_none(self._nanmean([b.fpr_at_tpr for b in self.breakdowns.get(c, [])])) for c in range(n_cls)],
+                "classes": self.classes})
         return models, {"mean_auc": mean_auc, "mean_avg_prec": mean_avg_prec, "std_auc": std_auc, "cls_aucs": cls_aucs}
 
     # ------------------------------------------------------------------------------------------- hot loop
@@ -526,6 +554,45 @@ class ADTrainer(ABC):
             return np.zeros(0, np.int64), 0, []
         per = min(len(rows) for _, rows, _ in lists)
         return np.concatenate([rows[:per] for _, rows, _ in lists]), per, [f"{name}: {num}" for name, _, num in lists]
+
+    def _check_breakdown_source(self, ds):
+        """`breakdown=True` only: refuse at the start of an evaluation a source that has forgotten its test rows' classes"""
+        if getattr(ds, "test_classes", None) is None:
+            raise NotImplementedError(f"breakdown=True needs a source with test_classes (the test rows' original class ids, as the "
+                                      f"sources of a LabelledImageSet carry them); {type(ds).__name__} has none")
+
+    def _log_breakdown(self, ds, la: np.ndarray, sc: torch.Tensor, idc: np.ndarray, nominal: int, cls: int, seed: int):
+        """the per-class breakdown of the test scores (`breakdown=True` only): kept, logged as JSON and as one text line"""
+        if sc.numel() == 0:
+            return None
+        ids = np.asarray(ds.test_classes)[idc]
+        names = getattr(ds, "classes", None) or getattr(self.dsstr, "classes", None) or self.classes
+        bd = class_breakdown(sc, ids, np.unique(ids[la == nominal]), tpr=self.breakdown_tpr, names=names)
+        self.breakdowns.setdefault(cls, []).append(bd)
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_breakdown", bd.to_json())
+        hard = bd.hardest()
+        if hard is not None:
+            self.logger.logtxt(f'Eval: hardest class is {hard[0]} "{hard[1]}" with {hard[2] * 100:04.2f}% AUC against its pool; '
+                               f'{bd.fpr_at_tpr * 100:04.2f}% FPR at {bd.tpr_level * 100:g}% TPR pooled (seed {seed}).')
+        return bd
+
+    @staticmethod
+    def _nanmean(values) -> float:
+        kept = [float(v) for v in values if v == v]
+        return float(np.mean(kept)) if kept else float("nan")
+
+    def breakdown_matrix(self) -> np.ndarray:
+        """float64 [no_classes, no_classes]: entry [c, k] is the mean over the seeds of the AUC of task c against class k
+        (`breakdown=True`; `self.breakdowns`), NaN where no seed has one: a task that did not run, a class that is not among the
+        trainer's classes' indices or not in the test split, a class whose pool was empty."""
+        n_cls = len(self.classes)
+        cells = [[[] for _ in range(n_cls)] for _ in range(n_cls)]
+        for c, per_seed in self.breakdowns.items():
+            for bd in per_seed:
+                for k, auc in zip(bd.classes, bd.auc):
+                    if 0 <= c < n_cls and 0 <= k < n_cls:
+                        cells[c][int(k)].append(auc)
+        return np.array([[self._nanmean(cell) for cell in row] for row in cells], dtype=np.float64).reshape(n_cls, n_cls)
 
     def _test_time_inputs(self, imgs: torch.Tensor, lbls: torch.Tensor, nominal: int) -> torch.Tensor:
         """the test-time steps between the loader and the encoder (`ad_trainer.py:501-505`): the test MSMs, then GCN"""
@@ -731,6 +798,8 @@ class ADTrainer(ABC):
             self._check_explainable(model, ds)
         if self.with_attention:
             self._check_explainable(model, ds, "attention", "whose attention could be rolled out")
+        if self.with_breakdown:
+            self._check_breakdown_source(ds)
         self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
         self._log_preview(ds, f"eval_cls{cls}-{clsstr}_preview", 20, False, seed)                         # :486-493
@@ -771,6 +840,8 @@ class ADTrainer(ABC):
                                f'{cls_prc.avg_prec * 100:04.2f}% average precision (seed {seed}).')
         else:
             cls_roc = cls_prc = None
+        if self.with_breakdown:
+            self._log_breakdown(ds, la, sc_t, idc, nominal, cls, seed)
         if self.with_histograms:                                                                        # :541-546
             self._log_histograms(la_t, sc_t, f"Eval: (SD{seed}) anomaly_scores cls{cls} nominal",
                                  f"Eval: (SD{seed}) anomaly_scores cls{cls} anomalous", 0)

@@ -895,6 +895,30 @@ int eoe_score_hist(const float* scores, const int64_t* labels, int n, const doub
 size_t eoe_score_extremes_scratch_bytes(int n, int k);
 int eoe_score_extremes(const float* scores, const int64_t* labels, int n, int k, int32_t* out_idx, float* out_val, int32_t* out_counts,
                        void* scratch, void* stream);
+/* The per-class breakdown of the scores (csrc/breakdown.hip): which class causes the misses.  Sample j has the dense class id
+ * class_ids[j] in [0, K) and the side side_per_class[class_ids[j]] (0 nominal, 1 anomalous; data.ad_targets).  The sub-problem of class
+ * k is class k against the pool of all samples of the other side, label 1 on the anomalous side; row K is the pooled problem (every
+ * anomalous sample against every nominal one).  The threshold of a problem is the score of the positive whose group of equal scores
+ * holds place m among the positives in descending order (gt < m <= ge; the bits of the group's smallest index; -0.0 == 0.0), where m
+ * is the caller's: m_per_class[k] for an anomalous class (its positives are the class), m_pooled for row K and for every nominal class
+ * (their positives are the whole anomalous side).  An m outside [1, number of positives] leaves the slot as cleared.
+ *   out_counts int64 [K+1][4], row k = { 2U, fps, tps, n_k }:
+ *       2U  = sum over (positive p, negative q) of 2 [s_p > s_q] + [s_p == s_q]: ROC AUC = 2U / (2 n_pos n_neg); row K: 0
+ *       fps = #{negatives: s >= threshold}, tps = #{positives: s >= threshold};  n_k = the size of class k; row K: 0
+ *   out_ap fp64 [K]: an anomalous class's average precision (1 / n_k) sum over p in k of ge_own(p) / (ge_own(p) + ge_pool(p)), ge_x(p) =
+ *       #{j in x: s_j >= s_p}; a fixed summation order (two runs give the same bits); 0 for a nominal class (not built: it would take a
+ *       count per (pool sample, class)) and for a class without samples.
+ *   out_thr fp32 [K+1]: the thresholds (a nominal class's is row K's).  Rows without a writer read as 0: the caller knows the class
+ *       sizes and reports a problem with an empty side as NaN.
+ *   scores fp32 [n], class_ids int32 [n], side_per_class uint8 [K], m_per_class int32 [K]: all DEVICE, as are the outputs; 4-byte
+ *   aligned (out_counts, out_ap: 8-byte).  1 <= n <= 2^20, 1 <= K <= 1024, 0 <= m_pooled <= n.  A sample whose class id is outside
+ *   [0, K) is in no class and no pool.  Non-finite scores are the caller's to reject (nothing is written out of range).
+ *   Exact integer pair counts (n^2 compares over cdiv(n, 256) workgroups, no sort, no atomics), then one workgroup per class.
+ *   scratch: eoe_class_breakdown_scratch_bytes(n, K) bytes (0 for an n or K outside the ranges), 4-byte aligned, may be dirty.  Four
+ *   enqueues on `stream` (two memsets of the outputs and two launches); the thresholds stay on the device in between. */
+size_t eoe_class_breakdown_scratch_bytes(int n, int K);
+int eoe_class_breakdown(const float* scores, const int32_t* class_ids, const uint8_t* side_per_class, const int32_t* m_per_class,
+                        int m_pooled, int n, int K, int64_t* out_counts, double* out_ap, float* out_thr, void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
