@@ -28,6 +28,7 @@ extern int g_vit_side_stream;   // vit.cpp
 extern int g_attn_flags;        // attention.hip
 extern int g_tn256_launches;    // gemm_tn256.hip
 int g_nt_last_kernel = EOE_NT_KERNEL_NONE;      // diagnostics: eoe_get_option("nt_last_kernel"), the route of the last eoe_gemm_nt (host side only)
+int g_nt_last_form = 0;                         // diagnostics: eoe_get_option("nt_last_form"), mi * 16 + ni of that route's NtRoute
 extern int g_parity_flags;      // parity.hip
 template <typename T> int eoe_launch_nt256(const void* gemm_p, int epi, int mi, hipStream_t s);   // gemm256.hip
 bool eoe_w8_applies(const void* gemm_p, int epi);                                       // gemm_w8.hip
@@ -1029,6 +1030,7 @@ int launch_nt(const GemmP& p, int epi, int gather, hipStream_t s) {
     const int flags = g_nt_flags, ncu = num_cus();
     const NtRoute r = nt_route(p, epi, gather, flags, ncu);
     g_nt_last_kernel = r.kernel;
+    g_nt_last_form = r.mi * 16 + r.ni;
     switch (r.kernel) {
         case EOE_NT_KERNEL_NARROW_256x64:
         case EOE_NT_KERNEL_GATHER:
@@ -1206,6 +1208,7 @@ extern "C" int eoe_get_option(const char* name, int* value) {
     if (!strcmp(name, "attn_flags")) { *value = g_attn_flags; return 0; }
     if (!strcmp(name, "tn256_launches")) { *value = g_tn256_launches; return 0; }       // read-only diagnostics
     if (!strcmp(name, "nt_last_kernel")) { *value = g_nt_last_kernel; return 0; }       // read-only diagnostics: EOE_NT_KERNEL_*
+    if (!strcmp(name, "nt_last_form")) { *value = g_nt_last_form; return 0; }           // read-only diagnostics: mi * 16 + ni of the NtRoute
     if (!strcmp(name, "parity_flags")) { *value = g_parity_flags; return 0; }
     return eoe_set_error(EOE_ERR_ARG, "unknown option");
 }

@@ -1134,7 +1134,9 @@ int eoe_probe_copy(void* dst, const void* src, int64_t bytes, void* stream);
 int eoe_set_option(const char* name, int value);
 int eoe_get_option(const char* name, int* value);    /* the current value (callers that change a switch restore what they found) */
 /* "nt_last_kernel" (read-only diagnostics, like "tn256_launches"): the route the last eoe_gemm_nt of this process took, set on the host by the
- * launcher; tests assert it so that a case which falls through to another kernel fails instead of passing */
+ * launcher; tests assert it so that a case which falls through to another kernel fails instead of passing.
+ * "nt_last_form" (read-only, set with it): mi * 16 + ni of that route -- rows per tile / 32 of the two-workgroup and one-wave kernels, columns
+ * per tile / 32 of the persistent kernel; it tells the kernels behind EOE_NT_KERNEL_GATHER apart (0: the 256 x 64 kernel) */
 enum {
     EOE_NT_KERNEL_NONE = 0,                  /* no NT GEMM launched yet */
     EOE_NT_KERNEL_PERSISTENT_256x128 = 1,    /* gemm.hip: eight waves, one workgroup per CU, 256 x 128 tiles */

@@ -55,6 +55,8 @@ on the CU count (the 160 x 256 x 32 kernel; the eight-wave kernel's fall-backs c
 code from `dispatch(case, ncu)`, a Python restatement of nt_route's conditions (gemm.hip) that only builds tables: the CPU tests hold it
 against the real rule, asked through eoe_gemm_nt_route, on every row at 64 to 304 CUs, and the GPU tests assert that the route asked for is
 the route that ran (`nt_last_kernel`).
+The gather forms (the route "gather" of NT_KERNELS: the implicit patch matrix of a convolution, in eoe_gemm_nt and eoe_gemm_tn_grouped) are
+outside these tables: tests/conv_gather_util.py has theirs, bitwise on integer inputs, with the data-movement kernels of csrc/conv.hip.
 The wide-tile and stream-K TN forms need workload-sized groups (216 tiles of 256 x 128 on 256 CUs) and keep their present tests
 (test_gemm_tn_wide_tiles, test_gemm_tn_grouped_stream_k); nothing here shrinks them.
 
@@ -182,7 +184,8 @@ def _cdiv(a, b):
 
 
 def dispatch(c, ncu=DEFAULT_CUS):
-    """nt_route of gemm.hip for gather == 0 without the opt-in stream-K bits: the name of the route"""
+    """nt_route of gemm.hip for gather == 0 without the opt-in stream-K bits: the name of the route (the gather branches:
+    conv_gather_util.route_form)"""
     f, k = c["flags"], kind_of(c)
     M, N, K = c["M"], c["N"], c["K"]
     if k["epi"] == "none" and N <= 64:

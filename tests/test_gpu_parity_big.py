@@ -90,7 +90,9 @@ def _fmt(a):
     ("fc2048", 200, 2048, 512, 1, 1, 1, 0, False), ("fc512to256", 256, 512, 256, 1, 1, 1, 0, False), ("c16to20", 2, 16, 20, 7, 3, 1, 1, False),
     # stride-2 dgrad as four parity-class GEMMs (even maps) + split k over few output tiles (the small maps of WideResNet at 32 x 32)
     ("s2map4", 16, 128, 256, 4, 3, 2, 1, False), ("s2map8x1", 8, 64, 128, 8, 1, 2, 0, False), ("map2", 64, 256, 256, 2, 3, 1, 1, False),
-    ("s2c64", 3, 64, 64, 12, 3, 2, 1, False), ("c3to32", 4, 3, 32, 16, 5, 1, 2, True)])
+    ("s2c64", 3, 64, 64, 12, 3, 2, 1, False), ("c3to32", 4, 3, 32, 16, 5, 1, 2, True),
+    # rectangular maps, H given as (H, W): an unread last row on one axis only ((H + 2 pad - k) % stride != 0 for H, not for W); a 1-wide map
+    ("rect_s2", 2, 64, 128, (14, 13), 3, 2, 1, False), ("onewide", 3, 32, 64, (9, 1), 3, 1, 1, False)])
 @pytest.mark.parametrize("kernels", ["mfma", "valu"])
 def test_conv_f32_kernels_vs_fp64(name, n, cin, cout, H, k, stride, pad, nchw, kernels):
     """the parity-mode fp32 convolution kernels (forward incl. fused Normalize on an NCHW image, dgrad incl. accumulate, wgrad)
@@ -108,7 +110,7 @@ def test_conv_f32_kernels_vs_fp64(name, n, cin, cout, H, k, stride, pad, nchw, k
 
 
 def _conv_f32_case(name, n, cin, cout, H, k, stride, pad, nchw, F, ops, lib, check, f32):
-    W = H
+    H, W = H if isinstance(H, tuple) else (H, H)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     x, xr = f32(f"p/{name}/x", (n, cin, H, W) if nchw else (n, H, W, cin), 1.0)
     w, wr = f32(f"p/{name}/w", (cout, cin, k, k), (1.0 / (k * k * cin)) ** 0.5)
@@ -176,7 +178,7 @@ def _conv_f32_case(name, n, cin, cout, H, k, stride, pad, nchw, F, ops, lib, che
             dx2 = torch.empty_like(dx)
             check(lib.eoe_conv_f32_dgrad(p(dy), p(w), p(dx2), geo, cout, 0, p(sk), sk.numel() * 4, None, st), "dgrad")
             assert torch.equal(dx, dx2)
-        if stride == 2 and H % 2 == 0:
+        if stride == 2 and H % 2 == 0 and W % 2 == 0:
             # the parity-class form enumerates a pixel's valid taps in the order the all-taps form meets them: the same bits (no split k)
             from eoe_amd import _lib
             flags = _lib.get_option("parity_flags")

@@ -32,12 +32,16 @@ def _nhwc(t):
     (2, 64, 128, 14, 1, 2, 0, 1.0, False),    # downsample 1x1 stride 2 (resnet.py:72-76)
     (2, 3, 64, 32, 7, 2, 3, 0.0, True),       # the stem (resnet.py:35,93-95) on a small image
     (2, 8, 64, 9, 3, 2, 1, 0.0, False),       # odd grid, narrow input (dgrad GEMM needs cout % 64 == 0)
+    # rectangular maps, H given as (H, W): the last row is never read on one axis only ((H + 2p - k) % s != 0 for H, not for W); a 1-wide map
+    (3, 64, 128, (14, 13), 3, 2, 1, 0.0, False),
+    (2, 64, 64, (9, 1), 3, 1, 1, 0.0, False),
 ])
 def test_conv_bn_general_vs_oracle(dtype, n, cin, cout, H, k, s, p, slope, is_image):
     import eoe_amd
     import eoe_amd.ops as ops
     eoe_amd.set_compute_dtype(dtype)
-    x, xr = f32("rc/x", (n, cin, H, H), 1.0)
+    H, W = H if isinstance(H, tuple) else (H, H)
+    x, xr = f32("rc/x", (n, cin, H, W), 1.0)
     w, wr = f32("rc/w", (cout, cin, k, k), (1.0 / (k * k * cin)) ** 0.5)
     g, gr = f32("rc/g", (cout,), 0.1, mean=1.0)
     b, br = f32("rc/b", (cout,), 0.1)
@@ -77,12 +81,15 @@ def test_conv_bn_general_vs_oracle(dtype, n, cin, cout, H, k, s, p, slope, is_im
                                                (2, 256, 64, 7, 3, 1, 1), (1, 64, 192, 30, 5, 1, 2), (3, 32, 64, 16, 5, 1, 2),
                                                (2, 16, 64, 11, 3, 1, 1), (2, 8, 64, 10, 3, 2, 1),
                                                # 1x1 maps under a padded kernel: the one-tap plain-GEMM shortcut (ops._single_pixel)
-                                               (37, 128, 192, 1, 3, 1, 1), (70, 64, 64, 1, 5, 1, 2), (256, 512, 512, 1, 3, 1, 1)])
+                                               (37, 128, 192, 1, 3, 1, 1), (70, 64, 64, 1, 5, 1, 2), (256, 512, 512, 1, 3, 1, 1),
+                                               # rectangular maps, H given as (H, W): an unread last row on one axis only; a 1-wide map
+                                               (3, 64, 128, (14, 13), 3, 2, 1), (4, 64, 64, (1, 9), 3, 1, 1)])
 def test_implicit_conv_equals_materialised(n, cin, cout, H, k, s, p):
     """the implicit-GEMM path (patches fetched inside the GEMM's LDS stage: forward, wgrad, stride-1 dgrad) against the
     materialised im2col / col2im path on the same 16-bit operands: same products, different summation order only"""
     import eoe_amd.ops as ops
-    x, _ = f32("ic/x", (n, H, H, cin), 1.0)
+    H, W = H if isinstance(H, tuple) else (H, H)
+    x, _ = f32("ic/x", (n, H, W, cin), 1.0)
     w, _ = f32("ic/w", (cout, cin, k, k), (1.0 / (k * k * cin)) ** 0.5)
     g, _ = f32("ic/g", (cout,), 0.1, mean=1.0)
     b, _ = f32("ic/b", (cout,), 0.1)
