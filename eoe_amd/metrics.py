@@ -16,7 +16,12 @@ stable argsorts for host arrays.
 
 Which class causes the misses -- per class of the test split the AUC, the FPR at a TPR level and the AP of that class against the
 pool of all samples of the other side, which the reference does not have -- is `class_breakdown`: `eoe_class_breakdown` (exact
-integer pair counts, one workgroup per class) for GPU tensors, sorts for host arrays."""
+integer pair counts, one workgroup per class) for GPU tensors, sorts for host arrays.
+
+How much of a difference between two AUCs is test-set sampling noise -- DeLong's confidence interval of an AUC and the paired test of
+K models scored on the same samples, which neither the reference nor sklearn has -- is `delong` / `AucTest`: `eoe_delong_counts`
+(per sample the doubled count of opposite-label samples it beats or ties, then their sums and cross sums: exact integers) for GPU
+tensors, `searchsorted` for host arrays; the numerators in Python integers and one division per entry on the host."""
 from typing import Optional
 
 import numpy as np
@@ -788,3 +793,215 @@ def class_breakdown(scores, classes, normal_classes, tpr: float = 0.95, names=No
         names = {}
     label = (lambda c: names.get(c, c)) if hasattr(names, "get") else (lambda c: names[c] if 0 <= c < len(names) else c)
     return Breakdown(present, [label(int(c)) for c in present], side, sizes, auc, aps, fpr, tpr, fpr_at_tpr, float(thr[K]), counts, thr)
+
+
+# ------------------------------------------------------------------------------------------------------ DeLong
+DELONG_MAX_N = BREAKDOWN_MAX_N    # eoe_delong_counts: the cap of eoe_class_breakdown
+DELONG_MAX_COLUMNS = 8            # score columns (models) per call
+DELONG_TILE = 256                 # the count pass: rows per workgroup and opposite-side scores per LDS tile
+
+
+def delong_slices(n: int, K: int) -> int:
+    """into how many slices `eoe_delong_counts` cuts the opposite side at n samples and K columns (`eoe_delong_slices`; 0 for an n or
+    K it refuses): a slice is ceil(tiles / slices) tiles of `DELONG_TILE` scores, so with more tiles than slices a workgroup walks
+    several tiles, and with more than one slice the partial counts of a row meet in one integer counter"""
+    from ._lib import lib
+    return int(lib.eoe_delong_slices(int(n), int(K)))
+
+
+def _pairs(K: int):
+    return [(k, l) for k in range(K) for l in range(k, K)]
+
+
+class AucTest:
+    """DeLong's estimate (DeLong, DeLong & Clarke-Pearson 1988) of the K ROC AUCs of K score columns over the same test samples and of
+    their covariance matrix: what a difference between two AUCs is worth on a test set of this size.
+
+      auc [K]   `roc_auc` of every column;  cov [K, K]  the AUCs' covariance;  var  its diagonal;  se  sqrt(var)
+      n_pos, n_neg   the numbers of label-1 and label-0 samples (any other label is in neither)
+      counts    the integer table everything is divided from: {"T_pos", "T_neg": int64 [K], "A", "B": int64 [K (K + 1) / 2] (upper
+                triangles, row by row), "n_pos", "n_neg"}
+
+    Stated over doubled counts -- a[k,i] = 2 #{negatives below positive i} + #{negatives equal to it} in column k, b[k,j] the same for
+    negative j over the positives above and equal to it -- T[k] = sum a[k,:] = sum b[k,:], A[k,l] = sum_i a[k,i] a[l,i], B[k,l] =
+    sum_j b[k,j] b[l,j], m = n_pos, n0 = n_neg:
+        auc[k]   = T[k] / (2 m n0)
+        S10[k,l] = (m A[k,l] - T[k] T[l]) / (m (m - 1) 4 n0^2)        S01[k,l] = (n0 B[k,l] - T[k] T[l]) / (n0 (n0 - 1) 4 m^2)
+        cov[k,l] = S10[k,l] / m + S01[k,l] / n0
+    The numerators are formed in Python integers (T^2 passes 2^63) and every entry is one exactly rounded division, so nothing depends
+    on a summation order and an exact zero stays an exact zero.  With one positive or one negative the variance is undefined: `cov`,
+    `var` and `se` are NaN.
+
+    Positives {0.8, 0.6} against negatives {0.7, 0.5, 0.6}: a = {6, 3}, b = {2, 4, 3}, T = 9, auc = 9 / 12 = 0.75, S10 = (2 * 45 - 81) /
+    (2 * 1 * 4 * 9) = 0.125, S01 = (3 * 29 - 81) / (3 * 2 * 4 * 4) = 0.0625, var = 0.125 / 2 + 0.0625 / 3 = 1 / 12."""
+
+    def __init__(self, t_pos, t_neg, A, B, n_pos: int, n_neg: int):
+        from fractions import Fraction
+        self.n_pos, self.n_neg = int(n_pos), int(n_neg)
+        m, n0 = self.n_pos, self.n_neg
+        t_pos, t_neg, A, B = ([int(x) for x in np.asarray(v).ravel()] for v in (t_pos, t_neg, A, B))
+        K = len(t_pos)
+        if m < 1 or n0 < 1 or K < 1 or len(t_neg) != K or len(A) != len(B) or len(A) != K * (K + 1) // 2:
+            raise ValueError("an AUC test needs both classes and a table of K, K, K (K + 1) / 2 and K (K + 1) / 2 integers")
+        if t_pos != t_neg:
+            raise RuntimeError(f"the positives' pair counts {t_pos} and the negatives' {t_neg} differ: the count table is broken")
+        self.counts = {"T_pos": np.array(t_pos, np.int64), "T_neg": np.array(t_neg, np.int64), "A": np.array(A, np.int64),
+                       "B": np.array(B, np.int64), "n_pos": m, "n_neg": n0}
+        self.auc = np.array([t / (2 * m * n0) for t in t_pos], dtype=np.float64)       # int / int: one exactly rounded division
+        self.cov = np.full((K, K), np.nan)
+        self._cov = None                                                                # the exact entries, when they are defined
+        self._pair = {}
+        for p, (k, l) in enumerate(_pairs(K)):
+            self._pair[k, l] = self._pair[l, k] = p
+        if m > 1 and n0 > 1:
+            self._cov = {}
+            for p, (k, l) in enumerate(_pairs(K)):
+                tt = t_pos[k] * t_pos[l]
+                c = Fraction(m * A[p] - tt, m * (m - 1) * 4 * n0 * n0 * m) + Fraction(n0 * B[p] - tt, n0 * (n0 - 1) * 4 * m * m * n0)
+                self._cov[k, l] = self._cov[l, k] = c
+                self.cov[k, l] = self.cov[l, k] = float(c)
+        self.var = np.diagonal(self.cov).copy()
+        self.se = np.sqrt(self.var)
+
+    def cov_fraction(self, k: int, l: int):
+        """cov[k, l] as the exact rational number (`fractions.Fraction`); None where it is undefined"""
+        return None if self._cov is None else self._cov[k, l]
+
+    def ci(self, level: float = 0.95):
+        """(lo [K], hi [K]): auc -+ z se with z = NormalDist().inv_cdf((1 + level) / 2), clipped to [0, 1]; NaN where se is"""
+        from statistics import NormalDist
+        level = _check_level(level)
+        z = NormalDist().inv_cdf((1.0 + level) / 2.0)
+        return np.clip(self.auc - z * self.se, 0.0, 1.0), np.clip(self.auc + z * self.se, 0.0, 1.0)
+
+    def compare(self, k: int, l: int):
+        """the paired test of columns k and l: (diff = auc[k] - auc[l], z = diff / sqrt(var_diff), two-sided p = erfc(|z| / sqrt 2)) with
+        var_diff = cov[k,k] + cov[l,l] - 2 cov[k,l] (formed exactly before it is rounded: it cannot come out negative).  var_diff == 0:
+        z is 0 and p 1.0 where diff == 0, else z is +-inf and p 0.0.  Where the covariance is undefined (one positive or one negative):
+        (0.0, 0.0, 1.0) for two columns whose doubled counts agree sample by sample -- the difference is identically zero whatever
+        the variance -- and (diff, NaN, NaN) otherwise."""
+        import math
+        diff = float(self.auc[k] - self.auc[l])
+        if self._cov is None:
+            if all(int(self.counts[t][self._pair[k, k]]) == int(self.counts[t][self._pair[k, l]]) == int(self.counts[t][self._pair[l, l]])
+                   for t in ("A", "B")):                               # sum (a_k - a_l)^2 == 0 and sum (b_k - b_l)^2 == 0
+                return 0.0, 0.0, 1.0
+            return diff, float("nan"), float("nan")
+        var_diff = float(self._cov[k, k] + self._cov[l, l] - 2 * self._cov[k, l])
+        if var_diff == 0.0:
+            return (diff, 0.0, 1.0) if diff == 0.0 else (diff, math.copysign(math.inf, diff), 0.0)
+        z = diff / math.sqrt(var_diff)
+        return diff, z, math.erfc(abs(z) / math.sqrt(2.0))
+
+    def pvalues(self) -> np.ndarray:
+        """[K, K]: `compare(k, l)[2]` for every pair (1.0 on the diagonal)"""
+        K = self.auc.size
+        return np.array([[self.compare(k, l)[2] for l in range(K)] for k in range(K)], dtype=np.float64).reshape(K, K)
+
+    def to_json(self, level: float = 0.95) -> dict:
+        """ints, floats, lists and None (for NaN): strict JSON"""
+        num = lambda x: None if x != x else float(x)                                                 # noqa: E731
+        lo, hi = self.ci(level)
+        return {"auc": [num(x) for x in self.auc], "cov": [[num(x) for x in row] for row in self.cov], "var": [num(x) for x in self.var],
+                "se": [num(x) for x in self.se], "n_pos": self.n_pos, "n_neg": self.n_neg, "level": float(level),
+                "ci_lo": [num(x) for x in lo], "ci_hi": [num(x) for x in hi], "pvalues": [[num(x) for x in row] for row in self.pvalues()]}
+
+    def __repr__(self):
+        return f"AucTest(auc={self.auc.tolist()}, se={self.se.tolist()}, n_pos={self.n_pos}, n_neg={self.n_neg})"
+
+
+def _check_level(level) -> float:
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.integer, np.floating)) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"a confidence level must be in (0, 1), not {level!r}")
+    return float(level)
+
+
+def _delong_host(y: np.ndarray, s: np.ndarray):
+    """the table of `eoe_delong_counts` from sorts: (T_pos [K], T_neg [K], A [P], B [P], m, n0) for labels y [n] and scores s [K, n].
+    With `lt` and `le` the numbers of opposite-side scores below and at-or-below a score (two `searchsorted`), a positive's doubled
+    count is lt + le and a negative's 2 m - lt - le."""
+    pos, neg = y == 1, y == 0
+    m, n0 = int(pos.sum()), int(neg.sum())
+    a, b = np.empty((s.shape[0], m), np.int64), np.empty((s.shape[0], n0), np.int64)
+    for k, col in enumerate(s):
+        sp, sn = col[pos], col[neg]
+        if np.isnan(sp).any() or np.isnan(sn).any():
+            raise ValueError("scores contain NaN")
+        sorted_p, sorted_n = np.sort(sp), np.sort(sn)
+        a[k] = np.searchsorted(sorted_n, sp, side="left") + np.searchsorted(sorted_n, sp, side="right")
+        b[k] = 2 * m - np.searchsorted(sorted_p, sn, side="left") - np.searchsorted(sorted_p, sn, side="right")
+    pairs = _pairs(s.shape[0])
+    # int64 holds every sum: at most 16 n^3 / 27 < 2^63 for n <= 2^20
+    return (a.sum(axis=1), b.sum(axis=1), np.array([np.dot(a[k], a[l]) for k, l in pairs], np.int64),
+            np.array([np.dot(b[k], b[l]) for k, l in pairs], np.int64), m, n0)
+
+
+def _check_delong_shape(n: int, K: int, n_labels: int):
+    if K < 1 or K > DELONG_MAX_COLUMNS:
+        raise ValueError(f"an AUC test takes between 1 and {DELONG_MAX_COLUMNS} score columns, not {K}")
+    if n_labels != n:
+        raise ValueError(f"an AUC test needs as many labels as scores per column, not {n_labels} and {n}")
+    if n < 2 or n > DELONG_MAX_N:
+        raise ValueError(f"an AUC test takes between 2 and {DELONG_MAX_N} samples, not {n}")
+
+
+def delong_device(labels, scores):
+    """`eoe_delong_counts` on GPU-resident scores [n] or [K, n]: (T_pos int64 [K], T_neg int64 [K], A int64 [K (K + 1) / 2], B the same,
+    m, n0, the number of NaN scores) as host arrays and ints -- the raw table, unchecked.  16-bit scores are compared as float32.
+    `labels` may live on either device: at most one upload, one call (a memset and three launches) and ONE copy back."""
+    import torch
+    from ._lib import check, lib
+    if not _is_gpu_tensor(scores):
+        raise RuntimeError("delong_device needs GPU scores (delong takes host arrays as they are)")
+    sc = scores.detach()
+    sc = (sc.reshape(1, -1) if sc.dim() <= 1 else sc.reshape(sc.shape[0], -1)).contiguous().float()
+    K, n = int(sc.shape[0]), int(sc.shape[1])
+    la = torch.as_tensor(labels).reshape(-1).to(torch.int64).to(sc.device).contiguous()
+    _check_delong_shape(n, K, la.numel())
+    P = K * (K + 1) // 2
+    out = torch.empty(2 * K + 2 * P + 3, dtype=torch.int64, device=sc.device)
+    scratch = torch.empty(lib.eoe_delong_scratch_bytes(n, K), dtype=torch.uint8, device=sc.device)
+    with torch.cuda.device(sc.device):
+        check(lib.eoe_delong_counts(sc.data_ptr(), la.data_ptr(), n, K, out.data_ptr(), scratch.data_ptr(),
+                                    torch.cuda.current_stream(sc.device).cuda_stream), "eoe_delong_counts")
+    raw = out.cpu().numpy()
+    return (raw[:K].copy(), raw[K:2 * K].copy(), raw[2 * K:2 * K + P].copy(), raw[2 * K + P:2 * K + 2 * P].copy(),
+            int(raw[-3]), int(raw[-2]), int(raw[-1]))
+
+
+def delong(labels, scores) -> Optional[AucTest]:
+    """DeLong's confidence intervals and paired tests for the ROC AUCs of `scores` [n] or [K, n] -- K <= 8 models scored on the same n
+    samples in the same order -- against `labels` [n] (1: positive, 0: negative, anything else is ignored): see `AucTest`.  None when
+    there is no positive or no negative, as the trainer skips the AUC there.
+
+    GPU tensors, or a list of K GPU tensors of one length (stacked on the device), go through `eoe_delong_counts` (exact integer pair
+    counts; only 2 K + K (K + 1) + 3 integers come back); host arrays and CPU tensors through sorts.  Both give the same integers,
+    and everything after them is the same host code.  Scores are compared as float32 on the device; host float32 stays float32,
+    anything else is compared as float64.  -0.0 equals 0.0 and the infinities are ordinary values.
+
+    ValueError for a NaN score among the positives and negatives, for K outside [1, 8], for n outside [2, 2^20] and for another number
+    of labels than scores."""
+    if isinstance(scores, (list, tuple)) and len(scores) > 0 and all(_is_gpu_tensor(x) for x in scores):
+        import torch
+        if len({int(x.numel()) for x in scores}) != 1:
+            raise ValueError(f"the score columns must have one length, not {[int(x.numel()) for x in scores]}")
+        if len(scores) > DELONG_MAX_COLUMNS:
+            raise ValueError(f"an AUC test takes between 1 and {DELONG_MAX_COLUMNS} score columns, not {len(scores)}")
+        scores = torch.stack([x.detach().reshape(-1).float() for x in scores])
+    if _is_gpu_tensor(scores):
+        t_pos, t_neg, A, B, m, n0, bad = delong_device(labels, scores)
+        if bad:
+            raise ValueError("scores contain NaN")
+    else:
+        s = np.asarray(_to_host(scores)) if not isinstance(scores, (list, tuple)) else np.stack([np.asarray(_to_host(x)).ravel() for x in scores])
+        if s.ndim > 1 and s.shape[0] == 0:
+            _check_delong_shape(2, 0, 2)
+        s = s.reshape(1, -1) if s.ndim <= 1 else s.reshape(s.shape[0], -1)
+        if s.dtype != np.float32:
+            s = s.astype(np.float64)
+        y = np.asarray(_to_host(labels)).ravel()
+        _check_delong_shape(s.shape[1], s.shape[0], y.size)
+        t_pos, t_neg, A, B, m, n0 = _delong_host(y, s)
+    if m == 0 or n0 == 0:
+        return None
+    return AucTest(t_pos, t_neg, A, B, m, n0)

@@ -46,6 +46,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     of that class against the pool of all samples of the other side, counted on the device (`eoe_class_breakdown`,
     csrc/breakdown.hip), kept in `trainer.breakdowns`, logged as JSON, and after `run` as the task x class AUC matrix
     (`breakdown_matrix()`).  The reference has nothing of the kind.  Off by default; needs a source that kept its test classes.
+  * `auc_ci=level` says how much of a test AUC is test-set sampling noise: DeLong's confidence interval per evaluation and, after a
+    class's last seed, the paired test of the seeds' AUCs over the shared test split, from exact integer pair counts taken on the
+    device (`eoe_delong_counts`, csrc/delong.hip; `metrics.delong`), kept in `trainer.auc_tests` and logged as JSON.  The reference
+    has nothing of the kind.  Off by default.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -59,7 +63,7 @@ import torch
 
 from .. import ops, parallel
 from ..metrics import (ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve,
-                       score_extremes, score_histograms, class_breakdown)
+                       score_extremes, score_histograms, class_breakdown, delong, DELONG_MAX_COLUMNS)
 from ..msm import apply_msms, check_supported
 from ..normalize import GcnNormalize
 from ..optim import FusedAdam
@@ -151,7 +155,7 @@ class ADTrainer(ABC):
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
                  previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
-                 attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95):
+                 attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -222,7 +226,20 @@ class ADTrainer(ABC):
         `eval_cls{cls}_it{seed}_breakdown`, and one text line names the hardest class (lowest AUC).  After `run`,
         `breakdown_matrix()` is the [task, class] matrix of the seeds' mean AUCs, logged with the tasks' mean pooled FPRs as
         `breakdown_auc`.  `run` starts with an empty `self.breakdowns`.  Default off: no launch, no file, the same return values
-        and files as before."""
+        and files as before.
+
+        `auc_ci=level` (a confidence level in (0, 1), such as 0.95; anything else raises here): where `eval_cls` computes the AUC it
+        also calls `eoe_amd.metrics.delong` on the labels and scores it holds (device scores: one `eoe_delong_counts` call, a
+        handful of integers come back).  The returned `ROC` gains the attributes `ci` = (lo, hi) at that level, `se` and `var`; the
+        `AucTest`'s `to_json(level)` is logged as `eval_cls{cls}_it{seed}_auc_ci` and the `Eval:` text line ends with the interval.
+        The evaluation's scores stay on the device, and after the last seed of a class `run` tests the seeds against each other
+        in one call with one column per seed (the first 8 when there are more, with a logged note) -- the test split and its order
+        are the same for every seed -- keeps the `AucTest` in `self.auc_tests[cls]` and logs its AUCs, covariance matrix and
+        pairwise p-values as `eval_cls{cls}_auc_compare`: whether the seed-to-seed spread exceeds what the size of the test set
+        explains.  Seeds whose label vectors differ are not compared (one logged line).  The scores are kept only inside `run`, from
+        a class's first seed to its comparison; `eval_cls` called on its own keeps nothing.  A NaN test score costs that evaluation
+        its interval (one logged line, no attribute, no file) and its place in the comparison, not the run.  `run` starts with an
+        empty `self.auc_tests`.  Default None: no launch, no file, no attribute, the same text line."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -278,6 +295,11 @@ class ADTrainer(ABC):
             raise ValueError(f"breakdown_tpr must be in (0, 1], not {breakdown_tpr!r}")
         self.breakdown_tpr = float(breakdown_tpr)
         self.breakdowns = {}                                # cls -> [Breakdown per seed], filled by eval_cls when with_breakdown
+        if auc_ci is not None and (isinstance(auc_ci, bool) or not isinstance(auc_ci, (int, float)) or not 0.0 < auc_ci < 1.0):
+            raise ValueError(f"auc_ci must be None or a confidence level in (0, 1), not {auc_ci!r}")
+        self.auc_ci = None if auc_ci is None else float(auc_ci)
+        self.auc_tests = {}                                 # cls -> AucTest over the seeds' scores, filled by run when auc_ci and seeds > 1
+        self._seed_scores = None                            # [(seed, labels, scores)] of the class `run` is at, while it has seeds to compare
 
     # ------------------------------------------------------------------------------------------- run
     def get_nominal_classes(self, cur_class: int):
@@ -395,9 +417,13 @@ class ADTrainer(ABC):
         self.explanations = {}
         self.attention_maps = {}
         self.breakdowns = {}
+        self.auc_tests = {}
+        self._seed_scores = None
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
+            # auc_ci: the seeds' scores are kept, where they are, only from here to the comparison below
+            self._seed_scores = [] if self.auc_ci is not None and test and run_seeds > 1 else None
             for seed in range(run_seeds):
                 self.logger.print(f'------ start training cls {c} "{cstr}" ------')
                 preset = None
@@ -419,6 +445,8 @@ class ADTrainer(ABC):
                     self.logger.snapshot(f"snapshot_cls{c}_it{seed}", model, epoch=self.epochs,
                                          ds_statistics=getattr(ds, "ds_statistics", None))
                 models[c].append(model if (model is None or ADTrainer.KEEP_SNAPSHOT_IN_RAM) else None)
+            if self._seed_scores is not None:
+                self._compare_seeds(c)
             if self.with_curves:
                 # the seeds' "mean" curves of this class, in the reference's order (:308-313; plot_many skips the seeds without a curve)
                 for k, lst in (("mean_train_rocs", train_rocs[c]), ("mean_eval_rocs", eval_rocs[c]), ("mean_eval_prcs", eval_prcs[c])):
@@ -580,6 +608,41 @@ class ADTrainer(ABC):
     def _nanmean(values) -> float:
         kept = [float(v) for v in values if v == v]
         return float(np.mean(kept)) if kept else float("nan")
+
+    def _log_auc_ci(self, roc: ROC, la: np.ndarray, la_t: torch.Tensor, sc_t: torch.Tensor, cls: int, seed: int) -> str:
+        """DeLong's interval of one evaluation's AUC (`auc_ci=level` only): attached to `roc`, logged as JSON, and returned as the
+        tail of the `Eval:` text line.  While `run` has seeds to compare, the scores are kept where they are.  A NaN score costs the
+        interval, not the run: one logged line, no attribute, no file."""
+        try:
+            test = delong(la_t, sc_t)                  # both classes are present: the caller has an AUC
+        except ValueError as e:
+            self.logger.logtxt(f"Eval: class {cls}, seed {seed}: no confidence interval of the AUC ({e}).")
+            return ""
+        (lo,), (hi,) = test.ci(self.auc_ci)
+        roc.ci, roc.se, roc.var = (float(lo), float(hi)), float(test.se[0]), float(test.var[0])
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_auc_ci", test.to_json(self.auc_ci))
+        if self._seed_scores is not None:
+            self._seed_scores.append((seed, la, sc_t.detach().reshape(-1).float()))
+        return f" {self.auc_ci * 100:g}% CI of the AUC [{lo * 100:04.2f}%, {hi * 100:04.2f}%]."
+
+    def _compare_seeds(self, cls: int):
+        """after a class's last seed (`auc_ci=level` only): the paired test of the seeds' AUCs over the shared test split"""
+        kept, self._seed_scores = self._seed_scores or [], None
+        if len(kept) < 2:
+            return
+        if len(kept) > DELONG_MAX_COLUMNS:
+            self.logger.logtxt(f"Eval: class {cls}: comparing the first {DELONG_MAX_COLUMNS} of {len(kept)} seeds' AUCs.")
+            kept = kept[:DELONG_MAX_COLUMNS]
+        labels = kept[0][1]
+        if any(not np.array_equal(la, labels) for _, la, _ in kept[1:]):
+            self.logger.logtxt(f"Eval: class {cls}: the seeds' test labels differ; their AUCs are not compared.")
+            return
+        scores = [sc for _, _, sc in kept]
+        test = delong(labels, scores if scores[0].is_cuda else torch.stack(scores).numpy())
+        if test is None:
+            return
+        self.auc_tests[cls] = test
+        self.logger.logjson(f"eval_cls{cls}_auc_compare", {"seeds": [s for s, _, _ in kept], **test.to_json(self.auc_ci)})
 
     def breakdown_matrix(self) -> np.ndarray:
         """float64 [no_classes, no_classes]: entry [c, k] is the mean over the seeds of the AUC of task c against class k
@@ -836,8 +899,9 @@ class ADTrainer(ABC):
                 else:
                     cls_roc.fpr, cls_roc.tpr, cls_roc.ths = roc_curve(la, sc)
                     cls_prc.prec, cls_prc.rec, cls_prc.ths = precision_recall_curve(la, sc)
+            interval = self._log_auc_ci(cls_roc, la, la_t, sc_t, cls, seed) if self.auc_ci is not None else ""
             self.logger.logtxt(f'Eval: class "{clsstr}" yields {cls_roc.auc * 100:04.2f}% AUC and '
-                               f'{cls_prc.avg_prec * 100:04.2f}% average precision (seed {seed}).')
+                               f'{cls_prc.avg_prec * 100:04.2f}% average precision (seed {seed}).' + interval)
         else:
             cls_roc = cls_prc = None
         if self.with_breakdown:

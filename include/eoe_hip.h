@@ -919,6 +919,27 @@ int eoe_score_extremes(const float* scores, const int64_t* labels, int n, int k,
 size_t eoe_class_breakdown_scratch_bytes(int n, int K);
 int eoe_class_breakdown(const float* scores, const int32_t* class_ids, const uint8_t* side_per_class, const int32_t* m_per_class,
                         int m_pooled, int n, int K, int64_t* out_counts, double* out_ap, float* out_thr, void* scratch, void* stream);
+/* DeLong's estimator of the covariance of K ROC AUCs measured on the same n samples, as exact integer sums (csrc/delong.hip).
+ * Positives: label 1 (m of them); negatives: label 0 (n0); any other label is in neither.  Per column k of scores and per sample
+ *       a[k,i] = 2 #{j negative: s_k[i] > s_k[j]} + #{j negative: s_k[i] == s_k[j]}   (positive i)
+ *       b[k,j] = 2 #{i positive: s_k[i] > s_k[j]} + #{i positive: s_k[i] == s_k[j]}   (negative j)
+ * with IEEE fp32 compares (-0.0 == 0.0, the infinities are ordinary values).  With P = K (K + 1) / 2:
+ *   out int64 [2K + 2P + 3] = { T_pos[K], T_neg[K], A[P], B[P], m, n0, nan }:
+ *       T_pos[k] = sum_i a[k,i] and T_neg[k] = sum_j b[k,j]: equal by construction, both written so that the caller can check;
+ *           ROC AUC_k = T[k] / (2 m n0)
+ *       A[k,l] = sum_i a[k,i] a[l,i], B[k,l] = sum_j b[k,j] b[l,j] for k <= l, the upper triangle row by row
+ *       nan = the number of NaN scores among the positives and negatives of all columns; when it is not 0 the sums are unspecified
+ *           (a NaN compares false; nothing is written out of range)
+ *   Every entry stays below 2^63: A, B <= 16 n^3 / 27 (4.4e14 at n = 90 000, 6.9e17 at n = 2^20).
+ *   scores fp32 [K][n] (column k at scores + k n), labels int64 [n], out: all DEVICE; 4-byte aligned (labels, out: 8-byte).
+ *   2 <= n <= 2^20, 1 <= K <= 8.  Integer compares and adds only (the atomics are integer adds): two runs give the same bytes.
+ *   scratch: eoe_delong_scratch_bytes(n, K) bytes (0 for an n or K outside the ranges), 4-byte aligned, may be dirty.  Four enqueues
+ *   on `stream` (a memset and three launches); m and n0 stay on the device in between.
+ * eoe_delong_slices: into how many slices the count pass cuts the opposite side at (n, K) (0 outside the ranges); rows and scores
+ *   are handled in blocks and tiles of 256. */
+size_t eoe_delong_scratch_bytes(int n, int K);
+int eoe_delong_slices(int n, int K);
+int eoe_delong_counts(const float* scores, const int64_t* labels, int n, int K, int64_t* out, void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
