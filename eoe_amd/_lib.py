@@ -20,6 +20,7 @@ EOE_MSM_FORM_NONE, EOE_MSM_FORM_DENSE, EOE_MSM_FORM_RANK = 0, 1, 2
 EOE_GCN_L1, EOE_GCN_L2 = 1, 2
 EOE_SALIENCY_MAX, EOE_SALIENCY_L2, EOE_SALIENCY_GRADXINPUT = 0, 1, 2
 EOE_FUSE_MEAN, EOE_FUSE_MAX, EOE_FUSE_MIN = 0, 1, 2
+EOE_CAM_GRADCAM, EOE_CAM_HIRESCAM = 0, 1
 EOE_COMM_I64, EOE_COMM_ID_BYTES, EOE_COMM_ALGO_RING, EOE_COMM_ALGO_RS_AG = 8, 128, 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD = 0, 1, 2, 3
 # EOE_NT_KERNEL_* (get_option("nt_last_kernel"): the route the last eoe_gemm_nt took; read-only diagnostics)
@@ -221,6 +222,7 @@ SIGNATURES = {
     "eoe_sgate_bwd": [C.POINTER(SGateBwdArgs), _vp],
     "eoe_cbam_junction_fwd": [C.POINTER(CGateArgs), C.POINTER(SGateArgs), _vp],
     "eoe_cbam_junction_bwd": [C.POINTER(CGateBwdArgs), C.POINTER(SGateBwdArgs), _vp, _vp, _vp, _vp],
+    "eoe_cbam_junction_bwd_data": [C.POINTER(CGateArgs), C.POINTER(SGateArgs)] + [_vp] * 11,
     "eoe_add_relu_fwd": [_vp, _vp, _vp, _vp, C.c_int, _i64, _vp],
     "eoe_relu_bwd": [_vp, _vp, _vp, _i64, _vp],
     "eoe_avgpool_fwd": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
@@ -283,6 +285,9 @@ SIGNATURES = {
     "eoe_attn_probs": [_vp, _vp] + [C.c_int] * 5 + [_vp],
     "eoe_rollout_step": [_vp, _vp, _vp, C.c_int, C.c_int, _f32, _vp],
     "eoe_rollout_map": [_vp, _vp] + [C.c_int] * 4 + [_vp],
+    "eoe_cam_weights": [_vp, _vp] + [C.c_int] * 4 + [_vp],
+    "eoe_cam_map": [_vp, _vp, _vp, _vp] + [C.c_int] * 5 + [_vp],
+    "eoe_cam_upsample": [_vp, _vp] + [C.c_int] * 5 + [_vp],
     "eoe_comm_unique_id": [_vp],
     "eoe_comm_init": [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
     "eoe_comm_destroy": [_vp],

@@ -435,10 +435,14 @@ __global__ __launch_bounds__(256) void sgate_bn_bwd_reduce_kernel(const float* _
     }
 }
 // dz[p] = gamma*rstd*(g - mean(g) - xhat*mean(g*xhat)) (training) or gamma*rstd*g (running statistics); in place over g
+// (SIG, the data-only backward over the running statistics: g arrives as dscale and takes its s(1-s) here, the product
+//  sgate_bn_bwd_reduce_kernel would have stored -- that launch is not needed where neither mean is)
+template <bool SIG = false>
 __global__ __launch_bounds__(256) void sgate_bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ stats,
                                                                  const float* __restrict__ gamma, const float* __restrict__ red,
                                                                  int nparts, float* __restrict__ g, float* __restrict__ dgamma,
-                                                                 float* __restrict__ dbeta, size_t P, int training) {
+                                                                 float* __restrict__ dbeta, size_t P, int training,
+                                                                 const float* __restrict__ scale = nullptr) {
     __shared__ float l0[4], l1[4];
     const float mu = stats[0], rs = stats[1], ga = gamma ? gamma[0] : 1.f;
     // every workgroup adds the nparts partial pairs in the same order (a few KB from L2)
@@ -459,6 +463,10 @@ __global__ __launch_bounds__(256) void sgate_bn_bwd_apply_kernel(const float* __
     const float m0 = r0 / cnt, m1 = r1 / cnt;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
         const float xh = (z[p] - mu) * rs;
+        if (SIG) {
+            const float s = scale[p];
+            g[p] = g[p] * s * (1.f - s);
+        }
         g[p] = training ? ga * rs * (g[p] - m0 - xh * m1) : ga * rs * g[p];
     }
 }
@@ -1056,6 +1064,63 @@ extern "C" int eoe_cbam_junction_bwd(const eoe_cgate_bwd_args* cb, const eoe_sga
     EOE_CHECK_LAUNCH("cbam_mlp_wgrad");
     hipLaunchKernelGGL(cbam_bwd_apply_kernel, dim3(grid_for(P * C / 4)), dim3(256), 0, s, (const float*)g, (const float*)sb->dcomp,
                        (const float*)cg->scale, (const float*)cb->dpooled, (const int*)cg->argmax, cb->dx, cg->n, HW, C);
+    EOE_CHECK_LAUNCH("cbam_bwd_apply");
+    return 0;
+}
+
+// the data-only form (an explanation): g and dx of eoe_cbam_junction_bwd bit for bit, no parameter gradient, no weight-gradient launch
+// (hence no (H+6)(W+6) cap: only sgate_conv_bwd_weight_kernel holds a padded plane in LDS); over the running statistics no
+// sgate_bn_bwd_reduce_kernel either -- sgate_bn_bwd_apply_kernel<true> takes the gate's s(1-s) itself
+extern "C" int eoe_cbam_junction_bwd_data(const eoe_cgate_args* cg, const eoe_sgate_args* sg, const float* dout, const float* out, float* g,
+                                          float* dx, float* dscale, float* dpooled, float* dhidden, float* dsp, float* dcomp, float* red,
+                                          void* stream) {
+    EOE_CHECK_ARG(cg && sg && dout && out && g && dx, "cbam_junction_bwd_data: null args");
+    EOE_TRY(check_cgate(cg));
+    EOE_CHECK_ARG(dscale && dpooled && dhidden && dsp && dcomp && red, "cbam_junction_bwd_data: null scratch");
+    EOE_CHECK_ARG(sg->w && sg->argmax && sg->z && sg->stats && sg->scale, "cbam_junction_bwd_data: null sgate args");
+    EOE_CHECK_ARG(sg->n == cg->n && sg->H > 0 && sg->W > 0 && sg->H * sg->W == cg->HW && sg->C == cg->C,
+                  "cbam_junction: the two gates disagree on the shape");
+    hipStream_t s = (hipStream_t)stream;
+    const int cpb = chan_cpb(cg->C), C = cg->C, HW = cg->HW;
+    const size_t P = (size_t)cg->n * HW;
+    EOE_CHECK_ARG(P < 0x7fffffffull && P * C / 4 < 0x7fffffffull, "cbam_junction_bwd_data: too many elements");
+    {
+        ProfScope ps("sgate_bwd", 0, 16.0 * P * C, stream);
+        hipLaunchKernelGGL(cbam_relu_pix_reduce_kernel, dim3(grid_for(P * 16)), dim3(256), 0, s, dout, out, cg->x, (const float*)cg->scale, g,
+                           dsp, P, HW, C);
+        EOE_CHECK_LAUNCH("cbam_relu_pix_reduce");
+        if (sg->training) {
+            int gr = grid_for(P, EOE_SGATE_PARTIALS);
+            hipLaunchKernelGGL(sgate_bn_bwd_reduce_kernel, dim3(gr), dim3(256), 0, s, sg->z, sg->stats, sg->scale, dsp, red, P);
+            EOE_CHECK_LAUNCH("cbam_bn_bwd_reduce");
+            if (eoe_bn_sync_active()) {
+                hipLaunchKernelGGL(sgate_bn_bwd_total_kernel, dim3(1), dim3(256), 0, s, red, gr, (float)P);
+                EOE_CHECK_LAUNCH("cbam_bn_bwd_total");
+                EOE_TRY(eoe_bn_sync_allreduce(red, 3, 0, stream));
+                gr = -1;
+            }
+            hipLaunchKernelGGL(sgate_bn_bwd_apply_kernel<false>, dim3(grid_for(P)), dim3(256), 0, s, sg->z, sg->stats, sg->gamma, (const float*)red,
+                               gr, dsp, (float*)nullptr, (float*)nullptr, P, 1);
+        } else {
+            hipLaunchKernelGGL(sgate_bn_bwd_apply_kernel<true>, dim3(grid_for(P)), dim3(256), 0, s, sg->z, sg->stats, sg->gamma, (const float*)red,
+                               0, dsp, (float*)nullptr, (float*)nullptr, P, 0, (const float*)sg->scale);
+        }
+        EOE_CHECK_LAUNCH("cbam_bn_bwd_apply");
+        hipLaunchKernelGGL(sgate_conv_bwd_data_kernel, dim3(grid_for(P)), dim3(256), 0, s, (const float*)dsp, sg->w, dcomp, sg->n, sg->H, sg->W, 1,
+                           (const float*)sg->scale, (const int*)sg->argmax);
+        EOE_CHECK_LAUNCH("cbam_conv_bwd_data");
+    }
+    ProfScope ps("cgate_bwd", 0, 16.0 * P * C, stream);
+    int nz = 1;                                                 // the slicing of eoe_cbam_junction_bwd: the same sums in the same order
+    while (nz < EOE_CBAM_DSCALE_SLICES && (size_t)cg->n * (C / 4 / cpb) * nz < 1024 && HW / (nz * 2) >= 64) nz *= 2;
+    hipLaunchKernelGGL(cbam_chan_reduce_kernel, dim3(cg->n, C / 4 / cpb, nz), dim3(256), 0, s, (const float*)g, (const float*)dcomp, cg->x, dscale,
+                       HW, C, cpb);
+    EOE_CHECK_LAUNCH("cbam_chan_reduce");
+    hipLaunchKernelGGL(cgate_mlp_bwd_kernel, dim3(cg->n), dim3(256), (C + 2 * cg->Ch) * sizeof(float), s, cg->scale, cg->hidden, cg->w1, cg->w2,
+                       dscale, dhidden, dpooled, C, cg->Ch, nz);
+    EOE_CHECK_LAUNCH("cbam_mlp_bwd");
+    hipLaunchKernelGGL(cbam_bwd_apply_kernel, dim3(grid_for(P * C / 4)), dim3(256), 0, s, (const float*)g, (const float*)dcomp,
+                       (const float*)cg->scale, (const float*)dpooled, (const int*)cg->argmax, dx, cg->n, HW, C);
     EOE_CHECK_LAUNCH("cbam_bwd_apply");
     return 0;
 }

@@ -19,9 +19,20 @@ and, from the forward pass alone, attention rollout (Abnar & Zuidema 2020; csrc/
                                             patch-level map fp32 [n, H, W] (`eoe_rollout_map`): a form `overlay` takes
   attention_probs_np / attention_rollout_np the float64 numpy statements of the two
 
-WideResNet (and anything else with a BatchNorm that is not a CNN32's or CNN28's own) is not served: its residual junctions and CBAM
-gates have no eval-mode backward over the running statistics; `input_gradient` refuses it.  No BatchNorm encoder has attention to
-roll out.
+and, for the WideResNet + CBAM encoder, Grad-CAM (Selvaraju et al. 2017; csrc/gradcam.hip):
+
+  grad_cam(model, images, score_fn, layer, mode, size)
+                                            the activation A of `layerK` weighted by the gradient dA of the score at it, rectified and
+                                            upsampled onto the image, fp32 [n, H, W]: a form `overlay` takes.  'gradcam'
+                                            relu(sum_c mean_p(dA)_c A_c) (`eoe_cam_weights`, `eoe_cam_map`), 'hirescam' relu(sum_c dA_c A_c)
+                                            (`eoe_cam_map` alone); `eoe_cam_upsample` is interpolate(bilinear, align_corners=False).  The
+                                            backward from the score to the layer runs in eval mode and asks for no parameter gradient:
+                                            the conv units skip theirs, the CBAM junction takes `eoe_cbam_junction_bwd_data`
+  cam_np / bilinear_np / grad_cam_np        the numpy statements (sums in float64, rounded once)
+
+WideResNet is served by `grad_cam`, not by `input_gradient`: pixel gradients through 17 convolutions, three max / argmax gates per block and
+a stride-2 stem are noise, and `input_gradient` (like `explain=True`) keeps refusing it and anything else with a BatchNorm that is not a
+CNN32's or CNN28's own.  No BatchNorm encoder has attention to roll out.
 """
 import numpy as np
 import torch
@@ -31,6 +42,8 @@ from ._lib import check, lib
 
 MODES = {"max": _lib.EOE_SALIENCY_MAX, "l2": _lib.EOE_SALIENCY_L2, "gradxinput": _lib.EOE_SALIENCY_GRADXINPUT}
 FUSE = {"mean": _lib.EOE_FUSE_MEAN, "max": _lib.EOE_FUSE_MAX, "min": _lib.EOE_FUSE_MIN}
+CAM_MODES = {"gradcam": _lib.EOE_CAM_GRADCAM, "hirescam": _lib.EOE_CAM_HIRESCAM}
+CAM_LAYERS = ("layer1", "layer2", "layer3", "layer4")
 HEAT_COLOUR = (255.0, 0.0, 0.0)
 OBJECTIVES = ("hsc", "bce", "focal", "dsad", "dsvdd", "clip")
 
@@ -425,4 +438,188 @@ def attention_rollout(model: torch.nn.Module, images: torch.Tensor, fuse: str = 
                 tok = blk.forward_tokens(tok, n)
         maps = torch.empty((n, grid * patch, grid * patch), dtype=torch.float32, device=dev)
         check(lib.eoe_rollout_map(r[cur].data_ptr(), maps.data_ptr(), n, L, grid, patch, ops._stream()), "eoe_rollout_map")
+    return maps
+
+
+# ------------------------------------------------------------------------------------------------ Grad-CAM
+def cam_np(A: np.ndarray, dA: np.ndarray, mode: str = "gradcam") -> np.ndarray:
+    """numpy statement of `eoe_cam_weights` + `eoe_cam_map`: fp32 [n, h, w] from A and dA fp32 NHWC [n, h, w, C]; 'gradcam'
+    relu(sum_c alpha_c A_c) with alpha = the mean of dA over the pixels, 'hirescam' relu(sum_c dA_c A_c); every sum in float64, rounded
+    once (alpha is rounded to fp32 as the kernel stores it).  relu keeps a NaN."""
+    if mode not in CAM_MODES:
+        raise ValueError(f"grad_cam: mode {mode!r} is none of {tuple(CAM_MODES)}")
+    a, d = np.asarray(A, dtype=np.float32).astype(np.float64), np.asarray(dA, dtype=np.float32).astype(np.float64)
+    if a.ndim != 4 or a.shape != d.shape:
+        raise ValueError(f"grad_cam: A and dA must be NHWC of one shape, not {a.shape} and {d.shape}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        if mode == "gradcam":
+            alpha = d.mean(axis=(1, 2)).astype(np.float32).astype(np.float64)
+            m = np.einsum("nhwc,nc->nhw", a, alpha)
+        else:
+            m = (a * d).sum(axis=3)
+        m = np.where((m > 0) | np.isnan(m), m, 0.0)
+        return m.astype(np.float32)
+
+
+def _bilinear_axis(n_in: int, n_out: int):
+    """source indices i0, i1 and the weight of i1 per destination index, as `eoe_cam_upsample` takes them: ((2 d + 1) n_in - n_out) /
+    (2 n_out) clamped at 0, split in integers"""
+    d = np.arange(n_out, dtype=np.int64)
+    num, den = np.maximum((2 * d + 1) * n_in - n_out, 0), 2 * n_out
+    i0 = num // den
+    return i0, np.minimum(i0 + 1, n_in - 1), (num - i0 * den) / float(den)
+
+
+def bilinear_np(m: np.ndarray, H: int, W: int) -> np.ndarray:
+    """numpy statement of `eoe_cam_upsample` in float64, rounded once: [n, h, w] -> fp32 [n, H, W], the positions of
+    torch.nn.functional.interpolate(mode='bilinear', align_corners=False)"""
+    m = np.asarray(m, dtype=np.float64)
+    n, h, w = m.shape
+    if H < h or W < w:
+        raise ValueError(f"grad_cam: the target {H} x {W} is smaller than the map {h} x {w}")
+    y0, y1, ly = _bilinear_axis(h, H)
+    x0, x1, lx = _bilinear_axis(w, W)
+    ly, lx = ly[None, :, None], lx[None, None, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        top = (1 - lx) * m[:, y0][:, :, x0] + lx * m[:, y0][:, :, x1]
+        bot = (1 - lx) * m[:, y1][:, :, x0] + lx * m[:, y1][:, :, x1]
+        return ((1 - ly) * top + ly * bot).astype(np.float32)
+
+
+def grad_cam_np(A: np.ndarray, dA: np.ndarray, mode: str, H: int, W: int) -> np.ndarray:
+    """`cam_np` then `bilinear_np`, the map kept in float64 between the two"""
+    if mode not in CAM_MODES:
+        raise ValueError(f"grad_cam: mode {mode!r} is none of {tuple(CAM_MODES)}")
+    a, d = np.asarray(A, dtype=np.float64), np.asarray(dA, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = np.einsum("nhwc,nc->nhw", a, d.mean(axis=(1, 2))) if mode == "gradcam" else (a * d).sum(axis=3)
+        m = np.where((m > 0) | np.isnan(m), m, 0.0)
+    return bilinear_np(m, H, W)
+
+
+def cam_weights(dA: torch.Tensor) -> torch.Tensor:
+    """alpha fp32 [n, C], the mean of dA fp32 NHWC [n, h, w, C] over the pixels (`eoe_cam_weights`); device tensors only"""
+    ops._chk(dA)
+    n, h, w, C = dA.shape
+    alpha = torch.empty((n, C), dtype=torch.float32, device=dA.device)
+    with torch.cuda.device(dA.device):
+        check(lib.eoe_cam_weights(dA.data_ptr(), alpha.data_ptr(), n, h, w, C, ops._stream()), "eoe_cam_weights")
+    return alpha
+
+
+def cam_map(A: torch.Tensor, dA: torch.Tensor, mode: str = "gradcam") -> torch.Tensor:
+    """the map at the layer's resolution, fp32 [n, h, w], from A and dA fp32 NHWC [n, h, w, C] (C % 4 == 0): one launch for 'hirescam', two
+    for 'gradcam' (`eoe_cam_weights`, `eoe_cam_map`); CPU tensors go through `cam_np`"""
+    if mode not in CAM_MODES:
+        raise ValueError(f"grad_cam: mode {mode!r} is none of {tuple(CAM_MODES)}")
+    if A.dim() != 4 or A.shape != dA.shape:
+        raise ValueError(f"grad_cam: A and dA must be NHWC of one shape, not {tuple(A.shape)} and {tuple(dA.shape)}")
+    if not A.is_cuda:
+        return torch.from_numpy(cam_np(A.detach().numpy(), dA.detach().numpy(), mode))
+    a, d = A.detach().contiguous().float(), dA.detach().to(A.device).contiguous().float()
+    n, h, w, C = a.shape
+    m = torch.empty((n, h, w), dtype=torch.float32, device=a.device)
+    alpha = cam_weights(d) if mode == "gradcam" else None
+    with torch.cuda.device(a.device):
+        check(lib.eoe_cam_map(a.data_ptr(), d.data_ptr(), ops._p(alpha), m.data_ptr(), n, h, w, C, CAM_MODES[mode], ops._stream()), "eoe_cam_map")
+    return m
+
+
+def cam_upsample(m: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """bilinear [n, h, w] -> fp32 [n, H, W] (`eoe_cam_upsample`: interpolate's align_corners=False positions; h <= H, w <= W); CPU tensors go
+    through `bilinear_np`"""
+    if m.dim() != 3:
+        raise ValueError(f"grad_cam: a map must be [n, h, w], not {tuple(m.shape)}")
+    n, h, w = m.shape
+    if H < h or W < w:
+        raise ValueError(f"grad_cam: the target {H} x {W} is smaller than the map {h} x {w}")
+    if not m.is_cuda:
+        return torch.from_numpy(bilinear_np(m.detach().numpy(), H, W))
+    mm = m.detach().contiguous().float()
+    out = torch.empty((n, H, W), dtype=torch.float32, device=mm.device)
+    with torch.cuda.device(mm.device):
+        check(lib.eoe_cam_upsample(mm.data_ptr(), out.data_ptr(), n, h, w, int(H), int(W), ops._stream()), "eoe_cam_upsample")
+    return out
+
+
+def _wide_resnet(model: torch.nn.Module, who: str):
+    from .models.resnet import WideResNet
+    wrn = next((m for m in model.modules() if isinstance(m, WideResNet)), None)
+    if wrn is None:
+        raise NotImplementedError(f"{who}: {type(model).__name__} has no WideResNet whose layers could be mapped (Grad-CAM serves the "
+                                  "WideResNet + CBAM encoder; the ViT towers, CNN32 and CNN28 have input_gradient)")
+    return wrn
+
+
+def grad_cam(model: torch.nn.Module, images: torch.Tensor, score_fn, layer: str = "layer4", mode: str = "gradcam", size=None) -> torch.Tensor:
+    """Grad-CAM of the model's WideResNet, fp32 [n, H, W] (`size` = (H, W), default the images'): a form `overlay` takes.
+
+    `WideResNet.features(images, layer)` gives the activation A of `layerK` without a tape; a detached leaf of it (with its 16-bit copy) goes
+    through `WideResNet.head` -- and whatever the model wraps around the tower (`build_model`) -- with the tape on, and one
+    `torch.autograd.grad(out, leaf, seed)` gives dA.  The model runs in eval mode and no parameter requires a gradient meanwhile: the
+    conv units differentiate the running statistics and skip every parameter gradient, a CBAM junction takes its data-only backward
+    (`eoe_cbam_junction_bwd_data`), so no running buffer, no `.grad` and no byte of a registered gradient arena is touched; every
+    module's flag and every `requires_grad` is restored afterwards, also after an exception.  For 'layer4' the backward is pool and fc
+    only.  The backward is seeded as `input_gradient` seeds it: the package's gradient scale times a per-image power of two that brings
+    d score_i / d out_i to order one.  Both modes are positively homogeneous of degree 1 in dA, so the finished map is divided by that
+    factor exactly (powers of two).  mode 'gradcam': relu(sum_c alpha_c A_c), alpha the pixel mean of dA; 'hirescam': relu(sum_c dA_c A_c).
+    Refused before any launch: a model without a WideResNet (NotImplementedError), an unknown layer or mode (ValueError), a layer below
+    'layer4' of a model in one of the unfused CBAM forms (`ops_resnet.FUSE_CBAM = False`, `no_spatial`: they have no data-only backward),
+    CPU images as the model refuses them."""
+    from . import ops_resnet
+    wrn = _wide_resnet(model, "grad_cam")
+    if layer not in CAM_LAYERS:
+        raise ValueError(f"grad_cam: layer {layer!r} is none of {CAM_LAYERS}")
+    if mode not in CAM_MODES:
+        raise ValueError(f"grad_cam: mode {mode!r} is none of {tuple(CAM_MODES)}")
+    if layer != "layer4":
+        k = CAM_LAYERS.index(layer) + 1
+        later = [b for name in CAM_LAYERS[k:] for b in getattr(wrn, name)]
+        if not ops_resnet.FUSE_CBAM or any(b.cbam is None or b.cbam.no_spatial for b in later):
+            raise NotImplementedError("grad_cam: below layer4 the backward crosses CBAM junctions, and only the fused unit has a data-only "
+                                      "backward (ops_resnet.FUSE_CBAM = False and no_spatial are not served)")
+    if images.dim() != 4:
+        raise ValueError(f"grad_cam: images must be [n, 3, H, W], not {tuple(images.shape)}")
+    H, W = (int(images.shape[2]), int(images.shape[3])) if size is None else (int(size[0]), int(size[1]))
+    side = wrn.res >> (2 + CAM_LAYERS.index(layer))              # the stem divides by 4, every later layer by 2
+    if H < side or W < side:
+        raise ValueError(f"grad_cam: size {H} x {W} is smaller than {layer}'s map {side} x {side}")
+    flags = [(m, m.training) for m in model.modules()]
+    frozen = [p for p in model.parameters() if p.requires_grad]
+    model.eval()
+    try:
+        for p in frozen:
+            p.requires_grad_(False)
+        # the model runs once, whatever it wraps around the tower; the tower's own forward is cut at the layer: the first half without a
+        # tape, the second from a detached leaf
+        cut = {}
+
+        def halves(x):
+            with torch.no_grad():
+                cut["a"] = wrn.features(x, layer)
+            cut["leaf"] = wrn.leaf_of(cut["a"])
+            return wrn.head(cut["leaf"], layer)
+
+        with torch.enable_grad():
+            wrn.forward = halves
+            try:
+                out = model(images.detach())
+            finally:
+                del wrn.forward                                   # the instance attribute: the class's forward shows again
+            a, leaf = cut["a"], cut["leaf"]
+            o = out.detach().requires_grad_()
+            (df,) = torch.autograd.grad(score_fn(o).reshape(-1).sum(), o)
+            amax = df.abs().amax(dim=1)
+            live = torch.isfinite(amax) & (amax > 0)
+            expo = torch.where(live, torch.floor(torch.log2(torch.where(live, amax, torch.ones_like(amax)))), torch.zeros_like(amax))
+            expo = expo.clamp(-100.0, 100.0)
+            seed = df * (torch.exp2(-expo) * ops.grad_scale())[:, None]
+            (dA,) = torch.autograd.grad(out, leaf, grad_outputs=seed)
+        maps = cam_upsample(cam_map(a, dA, mode), H, W)
+        maps.mul_((torch.exp2(expo) / ops.grad_scale())[:, None, None])      # the seeds undone: powers of two, exact
+    finally:
+        for p in frozen:
+            p.requires_grad_(True)
+        for mod, was in flags:
+            mod.training = was
     return maps

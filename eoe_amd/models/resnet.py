@@ -135,6 +135,59 @@ class WideResNet(nn.Module):
             layers.append(block(self.inplanes, planes, use_cbam=att_type == 'CBAM'))
         return nn.Sequential(*layers)
 
+    LAYERS = ("layer1", "layer2", "layer3", "layer4")
+
+    def _layer_index(self, layer) -> int:
+        if isinstance(layer, int) and not isinstance(layer, bool) and 1 <= layer <= 4:
+            return layer
+        if layer in self.LAYERS:
+            return self.LAYERS.index(layer) + 1
+        raise ValueError(f"WideResNet: layer {layer!r} is none of {self.LAYERS} (or 1 ... 4)")
+
+    def _refresh_weight_copies(self):
+        # all 16-bit weight copies that the optimiser step made stale, in one launch (the 19 block / down-sampling convolutions)
+        ops.refresh_conv_weight_copies([m.weight for layer in (self.layer1, self.layer2, self.layer3, self.layer4)
+                                        for m in layer.modules() if isinstance(m, nn.Conv2d) and m.weight.shape[1] % 8 == 0
+                                        and m.weight.shape[2] != 7])
+
+    def features(self, x, layer="layer4"):
+        """the first half of `forward`: stem through `layerK` (layer = 'layerK' or K), the fp32 NHWC activation [n, h, w, C] that layer
+        hands on, its 16-bit copy attached as `._eoe16` as the next block reads it.  `head(features(x, k), k)` is `forward(x)`, bit
+        for bit."""
+        k = self._layer_index(layer)
+        if not x.is_cuda:
+            raise RuntimeError("eoe_amd.WideResNet runs on the GPU only (no CPU fallback)")
+        x = x.view(-1, 3, self.res, self.res)
+        self._refresh_weight_copies()
+        mp = self.maxpool
+        x = _conv_bn(x, self.conv1, self.bn1, self.training, 0.0, is_image=True, normalize=self.normalize, want16=True,
+                     pool=(mp.kernel_size, mp.stride, mp.padding))
+        for name in self.LAYERS[:k]:
+            x = getattr(self, name)(x)
+        return x
+
+    def head(self, a, layer="layer4"):
+        """the second half of `forward`: the layers after `layerK`, then pool, `fc` and `linear`, from the activation `features` returns
+        (or a detached leaf of it that carries its `._eoe16` over: `leaf_of`)"""
+        k = self._layer_index(layer)
+        if not a.is_cuda:
+            raise RuntimeError("eoe_amd.WideResNet runs on the GPU only (no CPU fallback)")
+        self._refresh_weight_copies()
+        for name in self.LAYERS[k:]:
+            a = getattr(self, name)(a)
+        a = ops_resnet.GlobalAvgPoolFunction.apply(a)
+        a = ops.linear(a, self.fc.weight, self.fc.bias)
+        return ops.linear(a, self.linear.weight, self.linear.bias) if self.clf else a
+
+    @staticmethod
+    def leaf_of(a):
+        """a detached leaf of an activation that requires a gradient and keeps the 16-bit copy the next block reads"""
+        leaf = a.detach().requires_grad_()
+        a16 = getattr(a, "_eoe16", None)
+        if a16 is not None:
+            leaf._eoe16 = a16
+        return leaf
+
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("eoe_amd.WideResNet runs on the GPU only (no CPU fallback)")

@@ -249,6 +249,16 @@ class CbamJunctionFunction(torch.autograd.Function):
         dsp = scratch("sg_dscale", (n, H, W), torch.float32, dev)
         dcomp = scratch("sg_dcomp4", (n, H, W, 4), torch.float32, dev)           # the unit's per-pixel record: 4 floats
         red = scratch("sg_red", (SGATE_RED,), torch.float32, dev)
+        if not any(ctx.needs_input_grad[2:9]):
+            # no parameter asks for a gradient (an explanation, explain.grad_cam): the data-only call -- no weight-gradient kernel, no
+            # gradient target (which, for a parameter without .grad, would be its registered arena view), no cap on the map
+            w1c, b1c, w2c, b2c, wc = (t.detach().contiguous() for t in (w1, b1, w2, b2, w))
+            cg = _lib.CGateArgs(_p(x), None, _p(w1c), _p(b1c), _p(w2c), _p(b2c), _p(pooled), _p(argmax_c), _p(hidden), _p(sc), n, H * W, Cc, Ch)
+            sg = _lib.SGateArgs(None, None, _p(wc), _p(bn_w), _p(bn_b), None, None, None, _p(comp), _p(argmax_p), _p(z), _p(stats),
+                                _p(sp), None, n, H, W, Cc, eps, momentum, 1 if training else 0, None, None, 0)
+            check(lib.eoe_cbam_junction_bwd_data(C.byref(cg), C.byref(sg), _p(dout), _p(out), _p(g), _p(dx), _p(dsc), _p(dpooled),
+                                                 _p(dhidden), _p(dsp), _p(dcomp), _p(red), _stream()), "eoe_cbam_junction_bwd_data")
+            return (dx, g) + (None,) * 11
         wpart = scratch("sg_wpart", (n, 98), torch.float32, dev)
         sums = scratch("sg_sums", (BN_SCRATCH,), torch.float32, dev)
         dw1, db1, dw2, db2, dw = (_grad_target(t) for t in (w1, b1, w2, b2, w))

@@ -42,6 +42,8 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     over those images (`eoe_amd.explain.attention_rollout`, csrc/rollout.hip) -- no backward, no dependence on the objective or on a
     saturated score -- kept in `trainer.attention_maps` and logged as a picture of its own.  Off by default; ViT encoders only;
     independent of `explain`.
+  * `cam=True` (with `extremes`) is the explanation of a WideResNet encoder: Grad-CAM maps of those images at `cam_layer`
+    (`eoe_amd.explain.grad_cam`, csrc/gradcam.hip), kept in `trainer.cams` and logged as a picture of its own.  Off by default.
   * `breakdown=True` says which class causes the misses: per class of the test split the AUC, the FPR at `breakdown_tpr` and the AP
     of that class against the pool of all samples of the other side, counted on the device (`eoe_class_breakdown`,
     csrc/breakdown.hip), kept in `trainer.breakdowns`, logged as JSON, and after `run` as the task x class AUC matrix
@@ -155,7 +157,8 @@ class ADTrainer(ABC):
                  msms=(), workers: int = 2, classes: List[str] = None, data_parallel: bool = False,
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
                  previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
-                 attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None):
+                 attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None,
+                 cam: bool = False, cam_layer: str = "layer4", cam_mode: str = "gradcam"):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -215,6 +218,14 @@ class ADTrainer(ABC):
         `eval_cls{cls}-{clsstr}_it{seed}_extremes_attn`, laid over the pictures like the heat maps.  `run` starts with an empty
         `self.attention_maps`.  Independent of `explain`; default off: no launch, no file, the same return values and files as
         before.
+
+        `cam=True` (needs `extremes` > 0, a WideResNet encoder and a source with `test_inputs(rows)`; refused the same way): the rows
+        of the extremes picture get their Grad-CAM maps (`eoe_amd.explain.grad_cam` at `cam_layer` -- 'layer1' ... 'layer4' -- in
+        `cam_mode` -- 'gradcam' or 'hirescam'; csrc/gradcam.hip): the activation of that layer weighted by the gradient of the score,
+        rectified and upsampled onto the image, the explanation a WideResNet gets in place of `explain`.  The maps are kept in
+        `self.cams[f"eval_cls{cls}_it{seed}"]`, fp32 [rows, H, W] on the device; an active logger with a source that offers
+        `test_pictures` gets `eval_cls{cls}-{clsstr}_it{seed}_extremes_cam`.  `run` starts with an empty `self.cams`.  Default off:
+        no launch, no file, the same return values and files as before.
 
         `breakdown=True` (needs a source with `test_classes`, the test rows' original class ids -- a `LabelledImageSet`'s sources have
         them; anything else raises at the start of `eval_cls`, before any scoring): after its metrics `eval_cls` breaks the test
@@ -290,6 +301,17 @@ class ADTrainer(ABC):
         if self.with_attention and self.n_extremes == 0:
             raise ValueError("attention=True rolls out the rows that extremes=k ranks: extremes must be at least 1")
         self.attention_maps = {}                            # the same keys -> fp32 [rows, H, W] rollout maps, filled by eval_cls when with_attention
+        self.with_cam = bool(cam)
+        if self.with_cam and self.n_extremes == 0:
+            raise ValueError("cam=True maps the rows that extremes=k ranks: extremes must be at least 1")
+        if self.with_cam:
+            from ..explain import CAM_LAYERS, CAM_MODES
+            if cam_layer not in CAM_LAYERS:
+                raise ValueError(f"cam_layer {cam_layer!r} is none of {CAM_LAYERS}")
+            if cam_mode not in CAM_MODES:
+                raise ValueError(f"cam_mode {cam_mode!r} is none of {tuple(CAM_MODES)}")
+        self.cam_layer, self.cam_mode = cam_layer, cam_mode
+        self.cams = {}                                      # the same keys -> fp32 [rows, H, W] Grad-CAM maps, filled by eval_cls when with_cam
         self.with_breakdown = bool(breakdown)
         if isinstance(breakdown_tpr, bool) or not isinstance(breakdown_tpr, (int, float)) or not 0.0 < breakdown_tpr <= 1.0:
             raise ValueError(f"breakdown_tpr must be in (0, 1], not {breakdown_tpr!r}")
@@ -416,6 +438,7 @@ class ADTrainer(ABC):
         self.extremes = {}
         self.explanations = {}
         self.attention_maps = {}
+        self.cams = {}
         self.breakdowns = {}
         self.auc_tests = {}
         self._seed_scores = None
@@ -674,6 +697,9 @@ class ADTrainer(ABC):
         from ..models.clip_vit import VisualTransformer
         if not hasattr(ds, "test_inputs"):
             raise NotImplementedError(f"{option}=True needs a source with test_inputs(rows); {type(ds).__name__} has none")
+        if option == "cam":
+            explain._wide_resnet(model, "cam=True")          # NotImplementedError without one
+            return
         if any(isinstance(m, VisualTransformer) for m in model.modules()):
             return
         # the BatchNorm CNNs (CNN32, CNN28) hand an input gradient back through their first convolution; they have no attention
@@ -695,6 +721,25 @@ class ADTrainer(ABC):
         if self.logger.active and hasattr(ds, "test_pictures"):
             attn = explain.overlay(maps, ds.test_pictures(rows), self.EXPLAIN_ALPHA)
             self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_attn", attn, nrow=per, rowheaders=heads)
+
+    def _log_cams(self, model, ds, ex, center, nominal: int, cls: int, clsstr: str, seed: int):
+        """Grad-CAM maps of the extremes picture's rows (`cam=True` only): kept, and logged as a picture under an active logger"""
+        from .. import explain
+        rows, per, heads = self._extreme_rows(ex)
+        if not per:
+            return
+        imgs, lbls, _ = ds.test_inputs(rows)
+        imgs = self._test_time_inputs(imgs.to(self.device), lbls, nominal)
+        prev_scale = ops.grad_scale()
+        try:
+            ops.set_grad_scale(ops.default_grad_scale())          # as in training: the 16-bit dY chain of fp16 compute must not underflow
+            maps = explain.grad_cam(model, imgs, explain.score_fn(self, center, nominal), layer=self.cam_layer, mode=self.cam_mode)
+        finally:
+            ops.set_grad_scale(prev_scale)
+        self.cams[f"eval_cls{cls}_it{seed}"] = maps
+        if self.logger.active and hasattr(ds, "test_pictures"):
+            cam = explain.overlay(maps, ds.test_pictures(rows), self.EXPLAIN_ALPHA)
+            self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_cam", cam, nrow=per, rowheaders=heads)
 
     def _log_explanations(self, model, ds, ex, center, nominal: int, cls: int, clsstr: str, seed: int):
         """heat maps of the extremes picture's rows (`explain=True` only): kept, and logged as a second picture under an active logger"""
@@ -861,6 +906,8 @@ class ADTrainer(ABC):
             self._check_explainable(model, ds)
         if self.with_attention:
             self._check_explainable(model, ds, "attention", "whose attention could be rolled out")
+        if self.with_cam:
+            self._check_explainable(model, ds, "cam", "")
         if self.with_breakdown:
             self._check_breakdown_source(ds)
         self._msm_source(ds)
@@ -916,6 +963,8 @@ class ADTrainer(ABC):
                 self._log_explanations(model, ds, ex, center, nominal, cls, clsstr, seed)
             if self.with_attention and ex is not None:
                 self._log_attention(model, ds, ex, nominal, cls, clsstr, seed)
+            if self.with_cam and ex is not None:
+                self._log_cams(model, ds, ex, center, nominal, cls, clsstr, seed)
         model.cpu()
         return cls_roc, cls_prc
 

@@ -823,6 +823,14 @@ int eoe_sgate_bwd(const eoe_sgate_bwd_args* a, void* stream);
 int eoe_cbam_junction_fwd(const eoe_cgate_args* cg, const eoe_sgate_args* sg, void* stream);
 int eoe_cbam_junction_bwd(const eoe_cgate_bwd_args* cb, const eoe_sgate_bwd_args* sb, const float* dout, const float* out, float* g,
                           void* stream);
+/* The data-only form of eoe_cbam_junction_bwd (an explanation: no parameter requires a gradient): g and dx as above, bit for bit, and
+ * nothing else.  cg / sg are the FORWARD argument blocks as saved (cg->out, sg->x, sg->out, sg->res, sg->out16, the running buffers and
+ * sg->sums unused); the scratch: dscale EOE_CBAM_DSCALE_SLICES slices of [n, C], dpooled [n, 2, C], dhidden [n, 2, Ch], dsp [n, H, W],
+ * dcomp [n, H, W, 4], red EOE_SGATE_RED floats (untouched unless sg->training).  No parameter gradient is written and no
+ * weight-gradient kernel is launched, so the map is not capped at (H + 6)(W + 6) <= 8192; with sg->training == 0 the BatchNorm takes its
+ * running statistics and the batch-mean reduction is not launched either. */
+int eoe_cbam_junction_bwd_data(const eoe_cgate_args* cg, const eoe_sgate_args* sg, const float* dout, const float* out, float* g, float* dx,
+                               float* dscale, float* dpooled, float* dhidden, float* dsp, float* dcomp, float* red, void* stream);
 
 /* out = relu(a + b) (resnet.py:146-147); g = dout * [out > 0] (the gradient of both summands) */
 int eoe_add_relu_fwd(const float* a, const float* b, float* out, void* out16 /* optional 16-bit copy */, int dtype,
@@ -1130,6 +1138,23 @@ enum { EOE_FUSE_MEAN = 0, EOE_FUSE_MAX = 1, EOE_FUSE_MIN = 2 };
 int eoe_attn_probs(const void* qkv, float* probs, int n, int L, int heads, int dtype, int fuse, void* stream);
 int eoe_rollout_step(const float* probs, const float* r_in, float* r_out, int n, int L, float residual, void* stream);
 int eoe_rollout_map(const float* r, float* maps, int n, int L, int grid, int patch, void* stream);
+
+/* Grad-CAM (csrc/gradcam.hip; Selvaraju et al. 2017) for the WideResNet + CBAM encoder: A = a layer's activation, dA = the gradient of the
+ * score at it, both fp32 NHWC [n, h, w, C], C % 4 == 0, h, w >= 1, 16-byte aligned, fewer than 2^31 elements.  All three check their
+ * arguments before any launch (EOE_ERR_ARG: a null pointer, C % 4, a misaligned pointer, 2^31 elements or more, H < h or W < w, an
+ * unknown mode); n == 0 returns 0 without one.  No atomics, every sum in an order that depends on the shape alone: the same bytes on
+ * every run.  fp32 operations without contraction.
+ *   eoe_cam_weights   alpha fp32 [n, C] = (1 / hw) sum_p dA[i, p, c]
+ *   eoe_cam_map       map fp32 [n, h, w]: EOE_CAM_GRADCAM relu(sum_c alpha[i, c] A[i, p, c]) (dA may be NULL), EOE_CAM_HIRESCAM
+ *        relu(sum_c dA[i, p, c] A[i, p, c]) (alpha may be NULL: no weights launch is needed).  relu keeps a NaN.
+ *   eoe_cam_upsample  out fp32 [n, H, W] from map fp32 [n, h, w], bilinear at the positions of interpolate(align_corners=False): source
+ *        index max((dst + 0.5) h / H - 0.5, 0), split exactly (in integers) into its integer part i0 and its fraction l1, the
+ *        neighbour i1 = min(i0 + 1, h - 1); out = l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11), l0 = 1 - l1.  Any h <= H <= 32768
+ *        and w <= W <= 32768, integer ratio or not; h == w == 1 gives a constant map, h == H and w == W a bit copy. */
+enum { EOE_CAM_GRADCAM = 0, EOE_CAM_HIRESCAM = 1 };
+int eoe_cam_weights(const float* dA, float* alpha, int n, int h, int w, int C, void* stream);
+int eoe_cam_map(const float* A, const float* dA, const float* alpha, float* map, int n, int h, int w, int C, int mode, void* stream);
+int eoe_cam_upsample(const float* map, float* out, int n, int h, int w, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * in-library kernel timing (used by bench.py for the roofline line): while enabled, every entry point brackets
