@@ -1,0 +1,359 @@
+// Nearest neighbours between two sets of fp32 feature vectors: for every query row the k reference rows with the smallest squared
+// Euclidean distance, ascending by distance, equal distances by ascending reference index -- np.argsort(d2_row, kind="stable")[:k].
+// The nq x nr distance matrix is never written: a workgroup forms a 128 x 128 tile of it on the fp32 matrix cores and reduces it to
+// per-query candidate lists in LDS at once.
+//
+//   norms         one wave per row of q and of r: the sum of squares (an fmaf chain per lane, then a wave sum) and a flag for a row
+//                 that holds a NaN or an infinity, both written with ordinary stores.
+//   distances     d2 = (|q|^2 + |r|^2) - 2 q.r, clamped at 0.  The dot products run on v_mfma_f32_32x32x2_f32: fp32 in, fp32
+//                 accumulate, bit for bit a k-ordered fmaf chain (no 16-bit rounding enters a ranking).  A = references, B = queries,
+//                 so a lane of the result holds ONE query and 16 references: the tile goes to LDS as [reference][query] with the
+//                 query contiguous, free of bank conflicts on the way in and on the way out.
+//   tile          256 threads = 4 waves as 2 x 2, a wave 64 references x 64 queries = 2 x 2 MFMA tiles = 64 accumulator registers;
+//                 k-step 32 (operand tiles [32][129] floats each, k-major: an MFMA operand read is 32 consecutive floats per half
+//                 wave; the odd stride spreads the transposing stores of the 16-byte global loads over the banks).  The next k-step's
+//                 global loads are issued in front of the MFMAs of this one.  A D that is no multiple of 32 is zero-filled in LDS;
+//                 nothing is read past column D of a row.
+//   LDS           65 536 B (the distance tile; the operand tiles, 33 024 B, alias it) + 1 024 B (the tile's reference norms and
+//                 flags) + k * 8 B * 256 lists (k <= 32) or * 128 lists (k > 32): 76.8 KB at k = 5 (2 workgroups = 2 waves per SIMD),
+//                 132 KB at k = 64 (1 wave per SIMD; the fp32 MFMA reaches its rate from one wave with four accumulators).
+//   select        a workgroup takes 128 queries and one chunk of 1 024 references (8 tiles).  After a tile, one thread (k > 32) or
+//                 two threads (each half of the tile's references) per query walk its distances in ascending reference order and keep
+//                 the k smallest keys seen, key = ordered_bits(d2) << 32 | reference index (topk.hip's order-preserving image), in a
+//                 sorted list in LDS ([slot][thread]: lanes of a wave hit consecutive banks); the k-th key stays in a register, so a
+//                 candidate costs one compare unless it enters.  At the chunk's end the two lists of a query are merged and the k keys go
+//                 to scratch[nq][chunks][k] (an empty slot is all ones).
+//   merge         one wave per query: k rounds of "the smallest key above the last one" over its chunks * k keys, which are distinct,
+//                 then index and distance from the key.  Wave 0 also adds up the row flags into counts.
+// Integer compares only once a distance is formed, no atomics, every scratch word that is read is written first: two runs give the
+// same bytes and a dirty scratch changes nothing.  Three launches on the caller's stream.
+#include "common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int KN_NT = 256;
+constexpr int KN_BM = 128;                     // queries per workgroup
+constexpr int KN_BN = 128;                     // references per tile
+constexpr int KN_BK = 32;                      // k-step
+constexpr int KN_LD = 129;                     // operand tile row stride (floats)
+constexpr int KN_CHUNK = 1024;                 // references per workgroup
+constexpr int KN_K_MAX = 64;
+constexpr int KN_D_MAX = 2048;
+constexpr int KN_NR_MAX = 1 << 24;
+constexpr unsigned long long KN_EMPTY = ~0ull;
+constexpr unsigned KN_INF_BITS = 0xFF800000u;  // ordered_bits(+inf): every eligible distance is at or below it
+
+__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+int knn_chunks(int nr) { return cdiv(nr, KN_CHUNK); }
+__host__ __device__ constexpr int knn_tpr(int k) { return k <= 32 ? 2 : 1; }           // selection threads per query
+size_t knn_lds_bytes(int k) { return (size_t)KN_BN * KN_BM * 4 + (size_t)k * KN_BM * knn_tpr(k) * 8; }
+
+struct KnnScratch {                            // byte offsets into the caller's scratch
+    size_t qn, rn, qf, rf, keys, total;
+};
+KnnScratch knn_layout(int nq, int nr, int k) {
+    KnnScratch s;
+    s.qn = 0;
+    s.rn = s.qn + align16((size_t)nq * 4);
+    s.qf = s.rn + align16((size_t)nr * 4);
+    s.rf = s.qf + align16((size_t)nq * 4);
+    s.keys = s.rf + align16((size_t)nr * 4);
+    s.total = s.keys + align16((size_t)nq * knn_chunks(nr) * k * 8) + 16;
+    return s;
+}
+
+__device__ __forceinline__ unsigned ordered_bits(float s) {      // topk.hip: ascending unsigned order = ascending float order
+    unsigned b = __float_as_uint(s);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float from_ordered_bits(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+
+// row `row` of x, columns [k, k + 4): zero past column D and for a row past the set.  `vec`: base 16-byte aligned and ld % 4 == 0.
+__device__ __forceinline__ float4 load_quad(const float* __restrict__ x, int ld, int row, int nrows, int k, int D, bool vec) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row < nrows && k < D) {
+        const float* p = x + (size_t)row * ld + k;
+        if (vec && k + 4 <= D) {
+            v = *reinterpret_cast<const float4*>(p);
+        } else {
+            v.x = p[0];
+            if (k + 1 < D) v.y = p[1];
+            if (k + 2 < D) v.z = p[2];
+            if (k + 3 < D) v.w = p[3];
+        }
+    }
+    return v;
+}
+
+// one wave per row of q (rows [0, nq)) and of r (rows [nq, nq + nr)): squared norm and the non-finite flag
+__global__ __launch_bounds__(KN_NT) void knn_norm_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ r, int ldr, int nq,
+                                                         int nr, int D, float* __restrict__ qn, float* __restrict__ rn, int* __restrict__ qf,
+                                                         int* __restrict__ rf) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (KN_NT / 64) + (threadIdx.x >> 6);
+    if (row >= (long long)nq + nr) return;
+    const bool isq = row < nq;
+    const int i = isq ? (int)row : (int)(row - nq);
+    const float* p = isq ? q + (size_t)i * ldq : r + (size_t)i * ldr;
+    float s = 0.f;
+    bool bad = false;
+    for (int c = lane; c < D; c += 64) {
+        const float v = p[c];
+        bad |= (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
+        s = fmaf(v, v, s);
+    }
+    s = wave_sum(s);
+    const bool any = __ballot(bad) != 0ull;
+    if (lane == 0) {
+        (isq ? qn : rn)[i] = s;
+        (isq ? qf : rf)[i] = any ? 1 : 0;
+    }
+}
+
+// keeps the k smallest keys in the sorted list L[slot * stride]; thr is its last slot
+__device__ __forceinline__ void knn_insert(unsigned long long* __restrict__ L, int stride, int k, unsigned long long key,
+                                           unsigned long long& thr) {
+    int s = k - 1;
+    while (s > 0) {
+        const unsigned long long p = L[(s - 1) * stride];
+        if (p <= key) break;
+        L[s * stride] = p;
+        --s;
+    }
+    L[s * stride] = key;
+    thr = L[(k - 1) * stride];
+}
+
+__global__ __launch_bounds__(KN_NT) void knn_tile_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ r, int ldr, int nq,
+                                                         int nr, int D, int k, int chunks, int vecq, int vecr,
+                                                         const float* __restrict__ qnorm, const float* __restrict__ rnorm,
+                                                         const int* __restrict__ rflag, unsigned long long* __restrict__ keys) {
+    extern __shared__ __attribute__((aligned(16))) char kn_lds[];
+    __shared__ float rn_s[KN_BN];
+    __shared__ int rok_s[KN_BN];
+    float* stage = reinterpret_cast<float*>(kn_lds);                          // [KN_BN references][KN_BM queries]
+    float* As = stage;                                                        // [KN_BK][KN_LD] references, aliases the stage
+    float* Bs = stage + KN_BK * KN_LD;                                        // [KN_BK][KN_LD] queries
+    unsigned long long* lists = reinterpret_cast<unsigned long long*>(kn_lds + (size_t)KN_BN * KN_BM * 4);
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wr = wave >> 1, wq = wave & 1;                                  // the wave's 64 references x 64 queries of the tile
+    const int ch = (int)(blockIdx.x % (unsigned)chunks), qb = (int)(blockIdx.x / (unsigned)chunks);
+    const int q0 = qb * KN_BM;
+    const int tpr = knn_tpr(k), nsel = KN_BM * tpr, per = KN_BN / tpr;
+    const int lk = (t & 7) * 4, lrow = t >> 3;                                // loads: k quad and first row (then + 32)
+
+    unsigned long long thr = KN_EMPTY;
+    unsigned long long* mine = lists + t;
+    if (t < nsel)
+        for (int s = 0; s < k; ++s) mine[s * nsel] = KN_EMPTY;
+
+    float qn[2];
+#pragma unroll
+    for (int qi = 0; qi < 2; ++qi) {
+        const int qq = q0 + wq * 64 + qi * 32 + (lane & 31);
+        qn[qi] = qq < nq ? qnorm[qq] : 0.f;
+    }
+
+    const int nkt = (D + KN_BK - 1) / KN_BK;
+    for (int tile = 0; tile < KN_CHUNK / KN_BN; ++tile) {
+        const int r0 = ch * KN_CHUNK + tile * KN_BN;
+        if (r0 >= nr) break;                                                  // uniform over the workgroup
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+        float4 ra[4], rb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ra[j] = load_quad(r, ldr, r0 + lrow + 32 * j, nr, lk, D, vecr != 0);
+            rb[j] = load_quad(q, ldq, q0 + lrow + 32 * j, nq, lk, D, vecq != 0);
+        }
+        for (int kt = 0; kt < nkt; ++kt) {
+            __syncthreads();                                                  // the last reads of the operand tiles and of the stage are done
+            if (kt == 0 && t < KN_BN) {
+                const int rr = r0 + t;
+                rn_s[t] = rr < nr ? rnorm[rr] : 0.f;
+                rok_s[t] = rr < nr ? (rflag[rr] == 0) : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = lrow + 32 * j;
+                As[(lk + 0) * KN_LD + row] = ra[j].x; As[(lk + 1) * KN_LD + row] = ra[j].y;
+                As[(lk + 2) * KN_LD + row] = ra[j].z; As[(lk + 3) * KN_LD + row] = ra[j].w;
+                Bs[(lk + 0) * KN_LD + row] = rb[j].x; Bs[(lk + 1) * KN_LD + row] = rb[j].y;
+                Bs[(lk + 2) * KN_LD + row] = rb[j].z; Bs[(lk + 3) * KN_LD + row] = rb[j].w;
+            }
+            __syncthreads();
+            if (kt + 1 < nkt) {
+                const int kk = (kt + 1) * KN_BK + lk;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ra[j] = load_quad(r, ldr, r0 + lrow + 32 * j, nr, kk, D, vecr != 0);
+                    rb[j] = load_quad(q, ldq, q0 + lrow + 32 * j, nq, kk, D, vecq != 0);
+                }
+            }
+            const float* ap = As + (lane >> 5) * KN_LD + wr * 64 + (lane & 31);
+            const float* bp = Bs + (lane >> 5) * KN_LD + wq * 64 + (lane & 31);
+#pragma unroll
+            for (int ks = 0; ks < KN_BK; ks += 2) {
+                const float a0 = ap[ks * KN_LD], a1 = ap[ks * KN_LD + 32];
+                const float b0 = bp[ks * KN_LD], b1 = bp[ks * KN_LD + 32];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+        }
+        __syncthreads();                                                      // every wave has read its operands: the stage may take their place
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int qi = 0; qi < 2; ++qi)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int rl = wr * 64 + ri * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+                    const int ql = wq * 64 + qi * 32 + (lane & 31);
+                    stage[rl * KN_BM + ql] = fmaf(-2.f, acc[ri][qi][e], qn[qi] + rn_s[rl]);
+                }
+        __syncthreads();
+        if (t < nsel) {
+            const int ql = t & (KN_BM - 1), c0 = (t >> 7) * per;
+            for (int c = c0; c < c0 + per; ++c) {
+                if (!rok_s[c]) continue;                                      // past the set or a non-finite row: never a candidate
+                float d = stage[c * KN_BM + ql];
+                if (!(d > 0.f)) d = (d != d) ? __uint_as_float(0x7F800000u) : 0.f;      // clamp at 0; inf - inf of finite rows counts as inf
+                const unsigned long long key = ((unsigned long long)ordered_bits(d) << 32) | (unsigned)(r0 + c);
+                if (key < thr && (unsigned)(key >> 32) <= KN_INF_BITS) knn_insert(mine, nsel, k, key, thr);
+            }
+        }
+    }
+    __syncthreads();
+    if (t < KN_BM) {
+        if (tpr == 2) {
+            const unsigned long long* other = lists + t + KN_BM;
+            for (int s = 0; s < k; ++s) {
+                const unsigned long long key = other[s * nsel];
+                if (key >= thr) break;                                        // the partner's list is ascending
+                knn_insert(mine, nsel, k, key, thr);
+            }
+        }
+        const int qq = q0 + t;
+        if (qq < nq) {
+            unsigned long long* out = keys + ((size_t)qq * chunks + ch) * k;
+            for (int s = 0; s < k; ++s) out[s] = mine[s * nsel];
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// one wave per query: the k smallest of its chunks * k distinct keys, ascending; wave 0 adds up the flags
+__global__ __launch_bounds__(64) void knn_merge_kernel(const unsigned long long* __restrict__ keys, int nq, int nr, int k, int chunks,
+                                                       const int* __restrict__ qflag, const int* __restrict__ rflag, int* __restrict__ idx,
+                                                       float* __restrict__ d2, int* __restrict__ counts) {
+    const int qq = blockIdx.x, lane = threadIdx.x;
+    if (qq == 0) {
+        int cq = 0, cr = 0;
+        for (int i = lane; i < nq; i += 64) cq += qflag[i];
+        for (int i = lane; i < nr; i += 64) cr += rflag[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cq += __shfl_xor(cq, o, 64);
+            cr += __shfl_xor(cr, o, 64);
+        }
+        if (lane == 0) { counts[0] = cq; counts[1] = cr; }
+    }
+    int* oi = idx + (size_t)qq * k;
+    float* od = d2 + (size_t)qq * k;
+    if (qflag[qq]) {
+        for (int s = lane; s < k; s += 64) { oi[s] = -1; od[s] = __uint_as_float(0x7FC00000u); }
+        return;
+    }
+    const unsigned long long* mk = keys + (size_t)qq * chunks * k;
+    const long long M = (long long)chunks * k;
+    unsigned long long prev = 0ull;
+    int s = 0;
+    for (; s < k; ++s) {
+        unsigned long long best = KN_EMPTY;
+        for (long long i = lane; i < M; i += 64) {
+            const unsigned long long key = mk[i];
+            if ((s == 0 || key > prev) && key < best) best = key;
+        }
+        best = wave_min_u64(best);
+        if (best == KN_EMPTY) break;
+        if (lane == 0) {
+            oi[s] = (int)(unsigned)(best & 0xFFFFFFFFull);
+            od[s] = from_ordered_bits((unsigned)(best >> 32));
+        }
+        prev = best;
+    }
+    for (int j = s + lane; j < k; j += 64) { oi[j] = -1; od[j] = __uint_as_float(0x7F800000u); }
+}
+
+bool knn_in_range(int nq, int nr, int D, int k) {
+    return nq >= 0 && nr >= 0 && nr < KN_NR_MAX && D >= 1 && D <= KN_D_MAX && k >= 1 && k <= KN_K_MAX;
+}
+
+}  // namespace
+
+extern "C" size_t eoe_feature_knn_scratch_bytes(int nq, int nr, int D, int k) {
+    return knn_in_range(nq, nr, D, k) ? knn_layout(nq, nr, k).total : 0;
+}
+
+extern "C" int eoe_feature_knn(const float* q, int ldq, const float* r, int ldr, int nq, int nr, int D, int k, int* idx, float* d2, int* counts,
+                               void* scratch, void* stream) {
+    EOE_CHECK_ARG(q && r && idx && d2 && counts && scratch, "feature_knn: null q, r, idx, d2, counts or scratch");
+    EOE_CHECK_ARG(k >= 1 && k <= KN_K_MAX, "feature_knn: k must be in [1, %d], not %d", KN_K_MAX, k);
+    EOE_CHECK_ARG(D >= 1 && D <= KN_D_MAX, "feature_knn: D must be in [1, %d], not %d", KN_D_MAX, D);
+    EOE_CHECK_ARG(ldq >= D, "feature_knn: ldq must be at least D = %d, not %d", D, ldq);
+    EOE_CHECK_ARG(ldr >= D, "feature_knn: ldr must be at least D = %d, not %d", D, ldr);
+    EOE_CHECK_ARG(nq >= 0, "feature_knn: nq must not be negative (%d)", nq);
+    EOE_CHECK_ARG(nr >= 0 && nr < KN_NR_MAX, "feature_knn: nr must be in [0, 2^24), not %d", nr);
+    EOE_CHECK_ARG(((uintptr_t)q & 3) == 0 && ((uintptr_t)r & 3) == 0 && ((uintptr_t)idx & 3) == 0 && ((uintptr_t)d2 & 3) == 0 &&
+                      ((uintptr_t)counts & 3) == 0 && ((uintptr_t)scratch & 15) == 0,
+                  "feature_knn: q, r, idx, d2 and counts must be 4-byte aligned, scratch 16-byte aligned");
+    const int chunks = knn_chunks(nr);
+    const long long blocks = (long long)cdiv(nq, KN_BM) * chunks;
+    EOE_CHECK_ARG(blocks < (1ll << 31) && (long long)nq + nr < (1ll << 31), "feature_knn: nq = %d with nr = %d is more than one launch covers", nq, nr);
+    if (nq == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const KnnScratch lay = knn_layout(nq, nr, k);
+    char* base = static_cast<char*>(scratch);
+    float* qn = reinterpret_cast<float*>(base + lay.qn);
+    float* rn = reinterpret_cast<float*>(base + lay.rn);
+    int* qf = reinterpret_cast<int*>(base + lay.qf);
+    int* rf = reinterpret_cast<int*>(base + lay.rf);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + lay.keys);
+    ProfScope ps("feature_knn", 2.0 * nq * (double)nr * D, 4.0 * ((double)nq + nr) * D, stream);
+    const long long rows = (long long)nq + nr;
+    hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)((rows + KN_NT / 64 - 1) / (KN_NT / 64))), dim3(KN_NT), 0, st, q, ldq, r, ldr, nq, nr, D,
+                       qn, rn, qf, rf);
+    EOE_CHECK_LAUNCH("feature_knn (norms)");
+    if (chunks > 0) {
+        static bool once = (hipFuncSetAttribute((const void*)knn_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)knn_lds_bytes(KN_K_MAX)), true);
+        (void)once;
+        const int vecq = ((uintptr_t)q & 15) == 0 && (ldq & 3) == 0, vecr = ((uintptr_t)r & 15) == 0 && (ldr & 3) == 0;
+        hipLaunchKernelGGL(knn_tile_kernel, dim3((unsigned)blocks), dim3(KN_NT), knn_lds_bytes(k), st, q, ldq, r, ldr, nq, nr, D, k, chunks,
+                           vecq, vecr, (const float*)qn, (const float*)rn, (const int*)rf, keys);
+        EOE_CHECK_LAUNCH("feature_knn (tiles)");
+    }
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)nq), dim3(64), 0, st, (const unsigned long long*)keys, nq, nr, k, chunks,
+                       (const int*)qf, (const int*)rf, idx, d2, counts);
+    EOE_CHECK_LAUNCH("feature_knn (merge)");
+    return 0;
+}

@@ -1201,6 +1201,55 @@ class ResidentImageSource:
         finally:
             self._defer = was
 
+    @property
+    def n_normal(self) -> int:
+        """the size of the normal training set (`normal_index`, or the whole resident normal set)"""
+        return len(self.normal) if self.normal_index is None else len(self.normal_index)
+
+    def normal_inputs(self, rows):
+        """(images, indices) of the listed rows of the normal TRAINING set (positions in [0, n_normal), any order, repeats allowed)
+        under the TEST transform -- the route `test_images` takes, applied to `self.normal`: the centre crop (a ragged set: at each
+        image's own origin) or CLIP's transform of the whole image where the test split gets it, Normalize as the test batches carry
+        it; no flip, no noise, no colour jitter, and no draw from any generator, so training after a call is bit for bit what it was.
+        `indices` are the rows of the resident normal set (through `normal_index`: the labelled set's training rows).  What the
+        nearest-neighbour search embeds as its reference set.  A ragged normal set under a clip_preprocessing stage that is not the
+        identity has no counterpart on the test route (the test split is resized once at construction) and raises."""
+        pos = torch.as_tensor(rows).to(torch.int64).cpu().reshape(-1)
+        n = self.n_normal
+        if len(pos) and (int(pos.min()) < 0 or int(pos.max()) >= n):
+            raise IndexError(f"normal_inputs: rows outside the normal training set of {n} images")
+        idx = pos if self.normal_index is None else self.normal_index[pos]
+        src = self.normal
+        px = self.clip_preprocessing
+        if isinstance(src, RaggedImageSet):
+            if px is not None:
+                raise NotImplementedError("normal_inputs: the test route resizes a ragged test split to CLIP's n_px once, at "
+                                          "construction; the ragged normal training set has no such copy, so its images under the "
+                                          "test transform are not built")
+            tl = torch.from_numpy(center_origins(src.sizes, self.crop))
+            p = torch.stack([idx, tl[idx, 0], tl[idx, 1], torch.zeros_like(idx)], dim=1).to(torch.int32).to(src.device)
+            return augment_batch(src, p, (self.crop, self.crop), *self._norm_args(), True, 0.0, 0), idx
+        Hs, Ws = src.shape[1], src.shape[2]
+        if px is not None and self._clip_px(Hs, src.shape[3]) is not None:
+            if Hs != Ws:
+                raise NotImplementedError(f"normal_inputs: CLIP's transform of a {Hs} x {Ws} normal set is not built (square images only)")
+            p = torch.zeros((len(idx), 4), dtype=torch.int32)
+            p[:, 0] = idx
+            return augment_resize_batch(src, p.to(src.device), Hs, px, *self._norm_args(), True, 0.0, 0), idx
+        side = self.crop if px is None else px
+        p = torch.stack([idx, torch.full_like(idx, (Hs - side) // 2), torch.full_like(idx, (Ws - side) // 2), torch.zeros_like(idx)],
+                        dim=1).to(torch.int32).to(src.device)
+        return augment_batch(src, p, (side, side), *self._norm_args(), True, 0.0, 0), idx
+
+    def normal_pictures(self, rows):
+        """`normal_inputs(rows)[0]` without the Normalize: fp32 NCHW in ToTensor's [0, 1] scale (as `test_pictures`)"""
+        was = getattr(self, "_defer", False)
+        self._defer = True
+        try:
+            return self.normal_inputs(rows)[0]
+        finally:
+            self._defer = was
+
     PREVIEW_SEED = 0x9E3779B1
 
     def preview(self, percls=40, train=True):

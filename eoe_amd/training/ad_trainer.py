@@ -158,7 +158,8 @@ class ADTrainer(ABC):
                  graph_steps: bool = False, sync_bn: bool = True, exact_bn="auto", curves: bool = False,
                  previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
                  attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None,
-                 cam: bool = False, cam_layer: str = "layer4", cam_mode: str = "gradcam"):
+                 cam: bool = False, cam_layer: str = "layer4", cam_mode: str = "gradcam", neighbors: int = 0,
+                 knn_baseline: bool = False):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -224,7 +225,15 @@ class ADTrainer(ABC):
         `cam_mode` -- 'gradcam' or 'hirescam'; csrc/gradcam.hip): the activation of that layer weighted by the gradient of the score,
         rectified and upsampled onto the image, the explanation a WideResNet gets in place of `explain`.  The maps are kept in
         `self.cams[f"eval_cls{cls}_it{seed}"]`, fp32 [rows, H, W] on the device; an active logger with a source that offers
-        `test_pictures` gets `eval_cls{cls}-{clsstr}_it{seed}_extremes_cam`.  `run` starts with an empty `self.cams`.  Default off:
+        `test_pictures` gets `eval_cls{cls}-{clsstr}_it{seed}_extremes_cam`.  `run` starts with an empty `self.cams`.  (`neighbors=k`,
+        k in [1, 64], needs `extremes` > 0, a source with `test_inputs` and `normal_inputs` and a model with a feature output: the
+        rows of the extremes picture and ALL normal training images under the test transform are embedded in the arithmetic `eval_cls`
+        scored in, and one `eoe_amd.neighbors.feature_knn` (csrc/knn.hip) finds each row's k nearest normal training images:
+        `self.neighbors[f"eval_cls{cls}_it{seed}"]`, `eval_cls{cls}_it{seed}_extremes_neighbors` as JSON with dataset indices, and with
+        `normal_pictures` the picture `eval_cls{cls}-{clsstr}_it{seed}_extremes_neighbors`, each row an image and its k neighbours.
+        `knn_baseline=True` (needs `neighbors`) scores the whole test split by the mean distance to its k nearest normal features,
+        the standard non-parametric baseline: AUC and AP in `self.knn_results[cls]`, `eval_cls{cls}_it{seed}_knn` and a text line.
+        Both default off: no launch, no file, the same lines and return values.)  Default off:
         no launch, no file, the same return values and files as before.
 
         `breakdown=True` (needs a source with `test_classes`, the test rows' original class ids -- a `LabelledImageSet`'s sources have
@@ -312,6 +321,18 @@ class ADTrainer(ABC):
                 raise ValueError(f"cam_mode {cam_mode!r} is none of {tuple(CAM_MODES)}")
         self.cam_layer, self.cam_mode = cam_layer, cam_mode
         self.cams = {}                                      # the same keys -> fp32 [rows, H, W] Grad-CAM maps, filled by eval_cls when with_cam
+        if isinstance(neighbors, bool) or not isinstance(neighbors, (int, np.integer)) or not 0 <= neighbors <= 64:
+            raise ValueError(f"neighbors must be an integer in [0, 64] (0: off), not {neighbors!r}")
+        self.n_neighbors = int(neighbors)
+        if self.n_neighbors > 0 and self.n_extremes == 0:
+            raise ValueError("neighbors=k finds the nearest normal training images of the rows that extremes=k ranks: extremes must "
+                             "be at least 1")
+        self.with_knn_baseline = bool(knn_baseline)
+        if self.with_knn_baseline and self.n_neighbors == 0:
+            raise ValueError("knn_baseline=True scores the test split by its neighbors=k nearest normal features: neighbors must be "
+                             "at least 1")
+        self.neighbors = {}                                 # f"eval_cls{c}_it{seed}" -> eoe_amd.neighbors.Neighbors, filled by eval_cls when n_neighbors > 0
+        self.knn_results = {}                               # cls -> {k, auc, avg_prec, n_normal, D} of the last seed, filled by eval_cls when with_knn_baseline
         self.with_breakdown = bool(breakdown)
         if isinstance(breakdown_tpr, bool) or not isinstance(breakdown_tpr, (int, float)) or not 0.0 < breakdown_tpr <= 1.0:
             raise ValueError(f"breakdown_tpr must be in (0, 1], not {breakdown_tpr!r}")
@@ -439,6 +460,8 @@ class ADTrainer(ABC):
         self.explanations = {}
         self.attention_maps = {}
         self.cams = {}
+        self.neighbors = {}
+        self.knn_results = {}
         self.breakdowns = {}
         self.auc_tests = {}
         self._seed_scores = None
@@ -765,6 +788,62 @@ class ADTrainer(ABC):
             heat = explain.overlay(maps, ds.test_pictures(rows), self.EXPLAIN_ALPHA)
             self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_heat", heat, nrow=per, rowheaders=heads)
 
+    def _check_embedding(self, model, ds, nominal: int):
+        """`neighbors=k` only: refuse at the start of an evaluation a model without a feature output (one test image is embedded)"""
+        imgs, lbls, _ = ds.test_inputs([0])
+        with torch.no_grad():
+            out = model(self._test_time_inputs(imgs.to(self.device), lbls, nominal))
+        if out.reshape(out.shape[0], -1).shape[1] < 2:
+            raise NotImplementedError(f"neighbors={self.n_neighbors} searches the encoder's feature space: a classifier head has no "
+                                      "embedding; use an objective with a feature output")
+
+    def _log_neighbors(self, model, ds, ex, la_t, test_feats, nominal: int, cls: int, clsstr: str, seed: int):
+        """the k nearest normal training images of the extremes picture's rows in feature space (`neighbors=k` only): kept, logged
+        as JSON and, under an active logger with `normal_pictures`, as a picture of each row's image followed by its neighbours;
+        with `knn_baseline=True` also the k-NN score of the whole test split against the same normal features"""
+        from .. import neighbors as knn
+        k = self.n_neighbors
+        rows, per, _ = self._extreme_rows(ex)
+        if not per:
+            return
+        n_normal = ds.n_normal
+        normal_ids = []
+
+        def normal_batches():
+            for lo in range(0, n_normal, self.batch_size):
+                imgs, ids = ds.normal_inputs(torch.arange(lo, min(lo + self.batch_size, n_normal)))
+                normal_ids.append(ids)
+                yield imgs, torch.full((imgs.shape[0],), nominal, dtype=torch.int64)
+
+        refs = knn.embed(model, normal_batches(), trainer=self, nominal=nominal)
+        queries = knn.embed(model, [ds.test_inputs(rows)[:2]], trainer=self, nominal=nominal)
+        neigh = knn.feature_knn(queries, refs, k)
+        normal_ids = torch.cat(normal_ids).cpu().numpy()
+        self.neighbors[f"eval_cls{cls}_it{seed}"] = neigh
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_extremes_neighbors", neigh.as_dict(row_ids=rows, ref_ids=normal_ids))
+        if self.logger.active and hasattr(ds, "test_pictures") and hasattr(ds, "normal_pictures"):
+            own = ds.test_pictures(rows)
+            idx = neigh.idx.cpu()
+            near = ds.normal_pictures(idx.clamp(min=0).reshape(-1))
+            if near.shape[1:] == own.shape[1:]:
+                near = near.reshape(len(rows), k, *own.shape[1:]) * (idx >= 0).to(near.device, near.dtype).reshape(len(rows), k, 1, 1, 1)
+                cells = torch.cat([own.unsqueeze(1), near], dim=1).reshape(-1, *own.shape[1:]).float()
+                self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_neighbors", cells, nrow=k + 1)
+        if not self.with_knn_baseline or test_feats is None:
+            return
+        score = knn.knn_score(knn.feature_knn(test_feats, refs, k), "mean")
+        la = la_t.to(score.device)
+        if not (int((la == 0).sum()) > 0 and int((la == 1).sum()) > 0):
+            return
+        if score.is_cuda:
+            auc, ap = auc_ap_device(la, score)
+        else:
+            auc, ap = roc_auc(la.numpy(), score.numpy()), average_precision(la.numpy(), score.numpy())
+        res = {"k": k, "auc": float(auc), "avg_prec": float(ap), "n_normal": int(n_normal), "D": int(refs.shape[1])}
+        self.knn_results[cls] = res
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_knn", res)
+        self.logger.logtxt(f'Eval: class "{clsstr}" (seed {seed}) (k-NN baseline: {auc * 100:04.2f}% AUC)')
+
     def make_optimizer(self, model: torch.nn.Module):
         """Adam for every encoder (ad_trainer.py:383); the CLIP objective overrides this with SGD-Nesterov (:380-381)"""
         return FusedAdam(model.parameters(), lr=self.lr, weight_decay=self.wdk, amsgrad=False)
@@ -910,13 +989,19 @@ class ADTrainer(ABC):
             self._check_explainable(model, ds, "cam", "")
         if self.with_breakdown:
             self._check_breakdown_source(ds)
+        if self.n_neighbors > 0:
+            for need in ("test_inputs", "normal_inputs"):
+                if not hasattr(ds, need):
+                    raise NotImplementedError(f"neighbors={self.n_neighbors} needs a source with {need}(rows); {type(ds).__name__} has none")
         self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
         self._log_preview(ds, f"eval_cls{cls}-{clsstr}_preview", 20, False, seed)                         # :486-493
         self._normalize_hook(model, ds)
         center = self.center
         nominal = getattr(ds, "nominal_label", 0)
-        ep_labels, ep_scores, ep_idcs = [], [], []
+        if self.n_neighbors > 0:
+            self._check_embedding(model, ds, nominal)
+        ep_labels, ep_scores, ep_idcs, ep_feats = [], [], [], []
         prev_parity = ops.parity_mode()
         ops.set_parity_mode(self._exact_bn_for(model) or prev_parity)      # scored in the arithmetic it was trained in
         try:
@@ -926,6 +1011,8 @@ class ADTrainer(ABC):
                 with torch.no_grad():
                     feats = model(imgs)
                 ep_scores.append(self.compute_anomaly_score(feats, center, inputs=imgs, nominal_label=nominal))
+                if self.with_knn_baseline:
+                    ep_feats.append(feats.detach().reshape(feats.shape[0], -1).float())
                 ep_labels.append(lbls)
                 ep_idcs.append(batch[2] if len(batch) > 2 else torch.arange(len(lbls)))
         finally:
@@ -965,6 +1052,8 @@ class ADTrainer(ABC):
                 self._log_attention(model, ds, ex, nominal, cls, clsstr, seed)
             if self.with_cam and ex is not None:
                 self._log_cams(model, ds, ex, center, nominal, cls, clsstr, seed)
+            if self.n_neighbors > 0 and ex is not None:
+                self._log_neighbors(model, ds, ex, la_t, torch.cat(ep_feats) if ep_feats else None, nominal, cls, clsstr, seed)
         model.cpu()
         return cls_roc, cls_prc
 

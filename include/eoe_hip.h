@@ -948,6 +948,24 @@ int eoe_class_breakdown(const float* scores, const int32_t* class_ids, const uin
 size_t eoe_delong_scratch_bytes(int n, int K);
 int eoe_delong_slices(int n, int K);
 int eoe_delong_counts(const float* scores, const int64_t* labels, int n, int K, int64_t* out, void* scratch, void* stream);
+/* Nearest neighbours in feature space (csrc/knn.hip): for every row of q the k rows of r with the smallest squared Euclidean distance,
+ * ascending by distance, equal distances by ascending reference index -- np.argsort(d2_row, kind="stable")[:k] -- each with its distance.
+ *   q fp32 [nq, D] with row stride ldq, r fp32 [nr, D] with row stride ldr (ldq, ldr >= D; nothing is read past column D of a row);
+ *   idx int32 [nq, k], d2 fp32 [nq, k], counts int32 [2] = { non-finite query rows, non-finite reference rows }.  All DEVICE, 4-byte
+ *   aligned; a 16-byte aligned base with ld % 4 == 0 takes 16-byte loads, anything else element loads with the same result.
+ *   d2 = (|q|^2 + |r|^2) - 2 q.r, clamped at 0, the dot product a k-ordered fp32 fmaf chain (v_mfma_f32_32x32x2_f32): within
+ *   (2 D + 8) 2^-24 (|q|^2 + |r|^2) of the exact distance.  The nq x nr matrix is never stored: a workgroup reduces 128 queries x 1 024
+ *   references to k keys (ordered distance bits, reference index) per query in LDS, a second kernel merges a query's chunks.
+ *   Fewer than k eligible references: the tail holds idx = -1, d2 = +inf.  A reference row that holds a NaN or an infinity is never
+ *   returned; a query row that holds one gets idx = -1, d2 = NaN throughout.
+ *   1 <= k <= 64, 1 <= D <= 2048, 0 <= nr < 2^24, nq >= 0; nq == 0 returns 0 without a launch (counts is then left alone).
+ *   EOE_ERR_ARG, naming the argument, before any launch otherwise.  Integer compares only behind the distance, no atomics: two runs
+ *   give the same bytes.
+ *   scratch: eoe_feature_knn_scratch_bytes(nq, nr, D, k) bytes (0 outside the ranges), 16-byte aligned, may be dirty.  Three launches
+ *   on `stream`. */
+size_t eoe_feature_knn_scratch_bytes(int nq, int nr, int D, int k);
+int eoe_feature_knn(const float* q, int ldq, const float* r, int ldr, int nq, int nr, int D, int k, int* idx, float* d2, int* counts,
+                    void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
