@@ -241,6 +241,10 @@ SIGNATURES = {
     "eoe_delong_counts": [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp],
     "eoe_feature_knn_scratch_bytes": [C.c_int] * 4,
     "eoe_feature_knn": [_vp, C.c_int, _vp, C.c_int] + [C.c_int] * 4 + [_vp] * 5,
+    "eoe_feature_moments_scratch_bytes": [C.c_int] * 2,
+    "eoe_feature_moments": [_vp, C.c_int, C.c_int, C.c_int] + [_vp] * 6,
+    "eoe_mahalanobis_score_scratch_bytes": [C.c_int] * 3,
+    "eoe_mahalanobis_score": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 4,
     "eoe_clip_fwd": [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "eoe_clip_bwd": [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "eoe_clip_score": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
@@ -310,7 +314,8 @@ SIGNATURES = {
 _RESTYPES = {"eoe_last_error": C.c_char_p, "eoe_conv_f32_wgrad_workspace": _sz, "eoe_rank_curves_scratch_bytes": _sz,
              "eoe_score_hist_scratch_bytes": _sz, "eoe_score_extremes_scratch_bytes": _sz,
              "eoe_class_breakdown_scratch_bytes": _sz, "eoe_delong_scratch_bytes": _sz,
-             "eoe_feature_knn_scratch_bytes": _sz}
+             "eoe_feature_knn_scratch_bytes": _sz, "eoe_feature_moments_scratch_bytes": _sz,
+             "eoe_mahalanobis_score_scratch_bytes": _sz}
 
 
 def header_symbols():

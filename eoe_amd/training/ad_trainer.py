@@ -159,7 +159,7 @@ class ADTrainer(ABC):
                  previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
                  attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None,
                  cam: bool = False, cam_layer: str = "layer4", cam_mode: str = "gradcam", neighbors: int = 0,
-                 knn_baseline: bool = False):
+                 knn_baseline: bool = False, mahalanobis_baseline: bool = False, mahalanobis_shrinkage="ledoit_wolf"):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -235,6 +235,14 @@ class ADTrainer(ABC):
         the standard non-parametric baseline: AUC and AP in `self.knn_results[cls]`, `eval_cls{cls}_it{seed}_knn` and a text line.
         Both default off: no launch, no file, the same lines and return values.)  Default off:
         no launch, no file, the same return values and files as before.
+
+        `mahalanobis_baseline=True` (independent of `extremes` and `neighbors`; needs a source with `normal_inputs` and a model with a
+        feature output, refused at the start of `eval_cls` otherwise): the Gaussian baseline in feature space.  All normal training
+        images under the test transform are embedded as for `neighbors` (once, when both are on), `eoe_amd.mahalanobis.fit_gaussian`
+        fits their mean and covariance (csrc/mahalanobis.hip; `mahalanobis_shrinkage`: "ledoit_wolf" or a number in [0, 1]) and the
+        Mahalanobis distance scores the test features `eval_cls` kept: `self.mahalanobis_results[cls]` = {shrinkage, auc, avg_prec,
+        n_normal, D, nonfinite}, `eval_cls{cls}_it{seed}_mahalanobis` and a text line.  Default off: no launch, no file, the same
+        lines and return values.
 
         `breakdown=True` (needs a source with `test_classes`, the test rows' original class ids -- a `LabelledImageSet`'s sources have
         them; anything else raises at the start of `eval_cls`, before any scoring): after its metrics `eval_cls` breaks the test
@@ -333,6 +341,12 @@ class ADTrainer(ABC):
                              "at least 1")
         self.neighbors = {}                                 # f"eval_cls{c}_it{seed}" -> eoe_amd.neighbors.Neighbors, filled by eval_cls when n_neighbors > 0
         self.knn_results = {}                               # cls -> {k, auc, avg_prec, n_normal, D} of the last seed, filled by eval_cls when with_knn_baseline
+        self.with_mahalanobis = bool(mahalanobis_baseline)
+        if self.with_mahalanobis:
+            from ..mahalanobis import check_shrinkage
+            check_shrinkage(mahalanobis_shrinkage)
+        self.mahalanobis_shrinkage = mahalanobis_shrinkage
+        self.mahalanobis_results = {}                       # cls -> {shrinkage, auc, avg_prec, n_normal, D, nonfinite} of the last seed, filled by eval_cls when with_mahalanobis
         self.with_breakdown = bool(breakdown)
         if isinstance(breakdown_tpr, bool) or not isinstance(breakdown_tpr, (int, float)) or not 0.0 < breakdown_tpr <= 1.0:
             raise ValueError(f"breakdown_tpr must be in (0, 1], not {breakdown_tpr!r}")
@@ -462,6 +476,7 @@ class ADTrainer(ABC):
         self.cams = {}
         self.neighbors = {}
         self.knn_results = {}
+        self.mahalanobis_results = {}
         self.breakdowns = {}
         self.auc_tests = {}
         self._seed_scores = None
@@ -788,16 +803,62 @@ class ADTrainer(ABC):
             heat = explain.overlay(maps, ds.test_pictures(rows), self.EXPLAIN_ALPHA)
             self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_extremes_heat", heat, nrow=per, rowheaders=heads)
 
-    def _check_embedding(self, model, ds, nominal: int):
-        """`neighbors=k` only: refuse at the start of an evaluation a model without a feature output (one test image is embedded)"""
-        imgs, lbls, _ = ds.test_inputs([0])
+    def _check_embedding(self, model, ds, nominal: int, what: str = None):
+        """`neighbors=k` and `mahalanobis_baseline=True` only: refuse at the start of an evaluation a model without a feature output
+        (one test image is embedded; a source without `test_inputs` gives the first normal training image)"""
+        if hasattr(ds, "test_inputs"):
+            imgs, lbls, _ = ds.test_inputs([0])
+        else:
+            imgs = ds.normal_inputs([0])[0]
+            lbls = torch.full((imgs.shape[0],), nominal, dtype=torch.int64)
         with torch.no_grad():
             out = model(self._test_time_inputs(imgs.to(self.device), lbls, nominal))
-        if out.reshape(out.shape[0], -1).shape[1] < 2:
-            raise NotImplementedError(f"neighbors={self.n_neighbors} searches the encoder's feature space: a classifier head has no "
-                                      "embedding; use an objective with a feature output")
+        width = out.reshape(out.shape[0], -1).shape[1]
+        if width < 2:
+            what = what or f"neighbors={self.n_neighbors} searches the encoder's feature space"
+            raise NotImplementedError(f"{what}: a classifier head has no embedding; use an objective with a feature output")
+        return width
 
-    def _log_neighbors(self, model, ds, ex, la_t, test_feats, nominal: int, cls: int, clsstr: str, seed: int):
+    def _normal_features(self, model, ds, nominal: int, kept: dict):
+        """(features fp32 [n_normal, D], dataset indices) of ALL normal training images under the test transform, embedded in batches
+        of the trainer's size; `kept` holds them for the evaluation that asked, so that `neighbors` and `mahalanobis_baseline` embed
+        them once"""
+        if "feats" not in kept:
+            from .. import neighbors as knn
+            n_normal = ds.n_normal
+            normal_ids = []
+
+            def normal_batches():
+                for lo in range(0, n_normal, self.batch_size):
+                    imgs, ids = ds.normal_inputs(torch.arange(lo, min(lo + self.batch_size, n_normal)))
+                    normal_ids.append(ids)
+                    yield imgs, torch.full((imgs.shape[0],), nominal, dtype=torch.int64)
+
+            kept["feats"] = knn.embed(model, normal_batches(), trainer=self, nominal=nominal)
+            kept["ids"] = torch.cat(normal_ids).cpu().numpy()
+        return kept["feats"], kept["ids"]
+
+    def _log_mahalanobis(self, model, ds, la_t, test_feats, nominal: int, cls: int, seed: int, clsstr: str, kept: dict):
+        """the Gaussian baseline (`mahalanobis_baseline=True` only): mean and shrunk covariance of the normal training features, the
+        Mahalanobis distance of the test features, its AUC and AP"""
+        from .. import mahalanobis as mh
+        if not (int((la_t == 0).sum()) > 0 and int((la_t == 1).sum()) > 0):          # nothing to rank: embed and fit nothing
+            return
+        refs, _ = self._normal_features(model, ds, nominal, kept)
+        gauss = mh.fit_gaussian(refs, shrinkage=self.mahalanobis_shrinkage)
+        score = mh.mahalanobis_score(mh.mahalanobis(test_feats, gauss))
+        la = la_t.to(score.device)
+        if score.is_cuda:
+            auc, ap = auc_ap_device(la, score)
+        else:
+            auc, ap = roc_auc(la.numpy(), score.numpy()), average_precision(la.numpy(), score.numpy())
+        res = {"shrinkage": float(gauss.shrinkage), "auc": float(auc), "avg_prec": float(ap), "n_normal": int(gauss.n),
+               "D": int(refs.shape[1]), "nonfinite": int(gauss.nonfinite)}
+        self.mahalanobis_results[cls] = res
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_mahalanobis", res)
+        self.logger.logtxt(f'Eval: class "{clsstr}" (seed {seed}) (Mahalanobis baseline: {auc * 100:04.2f}% AUC)')
+
+    def _log_neighbors(self, model, ds, ex, la_t, test_feats, nominal: int, cls: int, clsstr: str, seed: int, kept: dict):
         """the k nearest normal training images of the extremes picture's rows in feature space (`neighbors=k` only): kept, logged
         as JSON and, under an active logger with `normal_pictures`, as a picture of each row's image followed by its neighbours;
         with `knn_baseline=True` also the k-NN score of the whole test split against the same normal features"""
@@ -807,18 +868,9 @@ class ADTrainer(ABC):
         if not per:
             return
         n_normal = ds.n_normal
-        normal_ids = []
-
-        def normal_batches():
-            for lo in range(0, n_normal, self.batch_size):
-                imgs, ids = ds.normal_inputs(torch.arange(lo, min(lo + self.batch_size, n_normal)))
-                normal_ids.append(ids)
-                yield imgs, torch.full((imgs.shape[0],), nominal, dtype=torch.int64)
-
-        refs = knn.embed(model, normal_batches(), trainer=self, nominal=nominal)
+        refs, normal_ids = self._normal_features(model, ds, nominal, kept)
         queries = knn.embed(model, [ds.test_inputs(rows)[:2]], trainer=self, nominal=nominal)
         neigh = knn.feature_knn(queries, refs, k)
-        normal_ids = torch.cat(normal_ids).cpu().numpy()
         self.neighbors[f"eval_cls{cls}_it{seed}"] = neigh
         self.logger.logjson(f"eval_cls{cls}_it{seed}_extremes_neighbors", neigh.as_dict(row_ids=rows, ref_ids=normal_ids))
         if self.logger.active and hasattr(ds, "test_pictures") and hasattr(ds, "normal_pictures"):
@@ -993,6 +1045,8 @@ class ADTrainer(ABC):
             for need in ("test_inputs", "normal_inputs"):
                 if not hasattr(ds, need):
                     raise NotImplementedError(f"neighbors={self.n_neighbors} needs a source with {need}(rows); {type(ds).__name__} has none")
+        if self.with_mahalanobis and not hasattr(ds, "normal_inputs"):
+            raise NotImplementedError(f"mahalanobis_baseline=True needs a source with normal_inputs(rows); {type(ds).__name__} has none")
         self._msm_source(ds)
         _, loader = ds.loaders(self.batch_size, num_workers=self.workers, shuffle_test=False)
         self._log_preview(ds, f"eval_cls{cls}-{clsstr}_preview", 20, False, seed)                         # :486-493
@@ -1001,7 +1055,14 @@ class ADTrainer(ABC):
         nominal = getattr(ds, "nominal_label", 0)
         if self.n_neighbors > 0:
             self._check_embedding(model, ds, nominal)
+        if self.with_mahalanobis:
+            from ..mahalanobis import MAHALANOBIS_MAX_D
+            width = self._check_embedding(model, ds, nominal, "mahalanobis_baseline=True fits a Gaussian in the encoder's feature space")
+            if width > MAHALANOBIS_MAX_D:
+                raise NotImplementedError(f"mahalanobis_baseline=True fits a Gaussian in at most {MAHALANOBIS_MAX_D} dimensions; the "
+                                          f"model's features have {width}")
         ep_labels, ep_scores, ep_idcs, ep_feats = [], [], [], []
+        normal_kept = {}                               # the normal training features, embedded at most once (_normal_features)
         prev_parity = ops.parity_mode()
         ops.set_parity_mode(self._exact_bn_for(model) or prev_parity)      # scored in the arithmetic it was trained in
         try:
@@ -1011,7 +1072,7 @@ class ADTrainer(ABC):
                 with torch.no_grad():
                     feats = model(imgs)
                 ep_scores.append(self.compute_anomaly_score(feats, center, inputs=imgs, nominal_label=nominal))
-                if self.with_knn_baseline:
+                if self.with_knn_baseline or self.with_mahalanobis:
                     ep_feats.append(feats.detach().reshape(feats.shape[0], -1).float())
                 ep_labels.append(lbls)
                 ep_idcs.append(batch[2] if len(batch) > 2 else torch.arange(len(lbls)))
@@ -1053,7 +1114,9 @@ class ADTrainer(ABC):
             if self.with_cam and ex is not None:
                 self._log_cams(model, ds, ex, center, nominal, cls, clsstr, seed)
             if self.n_neighbors > 0 and ex is not None:
-                self._log_neighbors(model, ds, ex, la_t, torch.cat(ep_feats) if ep_feats else None, nominal, cls, clsstr, seed)
+                self._log_neighbors(model, ds, ex, la_t, torch.cat(ep_feats) if ep_feats else None, nominal, cls, clsstr, seed, normal_kept)
+        if self.with_mahalanobis and ep_feats:
+            self._log_mahalanobis(model, ds, la_t, torch.cat(ep_feats), nominal, cls, seed, clsstr, normal_kept)
         model.cpu()
         return cls_roc, cls_prc
 

@@ -966,6 +966,40 @@ int eoe_delong_counts(const float* scores, const int64_t* labels, int n, int K, 
 size_t eoe_feature_knn_scratch_bytes(int nq, int nr, int D, int k);
 int eoe_feature_knn(const float* q, int ldq, const float* r, int ldr, int nq, int nr, int D, int k, int* idx, float* d2, int* counts,
                     void* scratch, void* stream);
+/* The Gaussian baseline in feature space (csrc/mahalanobis.hip): the moments a mean and a Ledoit-Wolf covariance are made of, and the
+ * squared Mahalanobis distance.  Both matrix products are k-ordered fp32 fmaf chains (v_mfma_f32_32x32x2_f32).
+ * eoe_feature_moments: x fp32 [n, D] with row stride ld (ld >= D; nothing is read past column D of a row).  A row that holds a NaN or an
+ *   infinity is excluded; over the rows used:
+ *     counts int32 [2] = { rows used, rows excluded }
+ *     mean fp32 [D]    = column sum / rows used: the sum in float64 in a fixed order, the quotient rounded once to fp32
+ *     scatter f64 [D, D] = Z^T Z with z = x - mean formed in fp32 (no centred copy of x is stored): the rows are cut into slices, a
+ *         slice's sum is an fp32 fmaf chain in row order, the slices are added in ascending order in float64.  Only the 128 x 128 tiles
+ *         on or above the diagonal are computed, the lower half is their mirror image: symmetric bit for bit.  Each entry lies within
+ *         (n + 4) 2^-24 sum_i |z_ia z_ib| of the exact sum over the fp32 z.
+ *     m4 f64 [1]       = sum_i (|z_i|^2)^2; |z_i|^2 in fp32, one wave per row: an fmaf chain per lane over columns lane, lane + 64, ...,
+ *         then the wave's butterfly sum (relative error (ceil(D / 64) + 6) 2^-24 to first order); squared and added in float64 in a
+ *         fixed tree over the rows' positions
+ *   No row used (n == 0 included): mean, scatter and m4 are zeros.  The number of slices is a pure function of (n, D), chosen so that
+ *   tiles x slices is about 256 workgroups; the fp32 partial tiles in scratch take 26 MB at most, whatever n.
+ *   All DEVICE; x, mean, counts 4-byte aligned, scatter and m4 8-byte aligned; a 16-byte aligned x with ld % 4 == 0 takes 16-byte loads,
+ *   anything else element loads with the same result.  0 <= n <= 2^30, 1 <= D <= 2048.  Six launches on `stream`.
+ * eoe_mahalanobis_score: d2[i] = sum_j y_ij^2 with y_ij = sum_k W[j,k] (x[i,k] - mean[k]); x fp32 [nq, D] (row stride ldx), mean fp32 [D],
+ *   W fp32 [P, D] (row stride ldw; ldx, ldw >= D): the inverse Cholesky factor of the covariance (P == D) or any P directions.
+ *   d2 fp32 [nq]; count int32 [1] = query rows that hold a NaN or an infinity, whose d2 is NaN.  x - mean is formed in fp32 while a
+ *   tile is staged; y is never stored: a workgroup squares and adds 128 queries x 128 rows of W in registers, one fp32 partial per
+ *   (query, 128 rows of W) goes to scratch and a last kernel adds a query's partials in ascending order.  Within
+ *   2^-24 (2 (D + 2) sum_j |y_j| a_j + (P + 2) sum_j y_j^2), a_j = sum_k |W[j,k]| |x_k - mean_k|, of the exact value of the fp32 inputs.
+ *   lower != 0 (accepted only with P == D) promises W[j,k] == 0 for k > j and skips those k-steps; while every fp32 x - mean is finite (0 * z == 0) the bytes are
+ *   those of lower == 0.  1 <= D, P <= 2048, 0 <= nq <= 2^30; nq == 0 returns 0 without a launch (count is then left alone).  Three launches.
+ * Both: EOE_ERR_ARG, naming the argument, before any launch; no atomics, fixed orders: two runs give the same bytes.
+ *   scratch: eoe_feature_moments_scratch_bytes(n, D) / eoe_mahalanobis_score_scratch_bytes(nq, D, P) bytes (0 outside the ranges),
+ *   16-byte aligned, may be dirty. */
+size_t eoe_feature_moments_scratch_bytes(int n, int D);
+int eoe_feature_moments(const float* x, int ld, int n, int D, float* mean, double* scatter, double* m4, int* counts, void* scratch,
+                        void* stream);
+size_t eoe_mahalanobis_score_scratch_bytes(int nq, int D, int P);
+int eoe_mahalanobis_score(const float* x, int ldx, int nq, int D, const float* mean, const float* W, int ldw, int P, int lower, float* d2,
+                          int* count, void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
