@@ -33,10 +33,9 @@ constexpr int BD_NT = 256;                     // both passes: threads per workg
 constexpr int BD_N_MAX = 1 << 20;              // the cap of curves.hip
 constexpr int BD_K_MAX = 1024;                 // a dense class id fits the low 16 bits of the packed word
 constexpr unsigned BD_DEAD = 0xFFFFu;          // class field of a sample whose id is outside [0, K): it is in no class and no pool
-constexpr size_t BD_ALIGN = 256;
 constexpr int BD_COLS = 4;                     // out_counts[k] = {2U, fps, tps, n_k}
 
-size_t plane_bytes(int n) { return ((size_t)n * 4 + BD_ALIGN - 1) / BD_ALIGN * BD_ALIGN; }
+size_t plane_bytes(int n) { return align_up((size_t)n * 4, 256); }
 
 __device__ __forceinline__ unsigned pack_class(const int32_t* __restrict__ cls, const uint8_t* __restrict__ side, int j, int K) {
     const int c = cls[j];
@@ -109,21 +108,6 @@ __global__ __launch_bounds__(BD_NT) void breakdown_count_kernel(const float* __r
     }
 }
 
-// the sum of one value per thread over the workgroup in a fixed tree; the result in every thread
-template <typename T>
-__device__ __forceinline__ T block_tree_sum(T v, T* buf) {
-    buf[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int h = BD_NT / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) buf[threadIdx.x] += buf[threadIdx.x + h];
-        __syncthreads();
-    }
-    const T total = buf[0];
-    __syncthreads();                                         // buf is written again by the next sum
-    return total;
-}
-
 __global__ __launch_bounds__(BD_NT) void breakdown_reduce_kernel(const float* __restrict__ s, const uint8_t* __restrict__ side, int n, int K,
                                                                  const unsigned* __restrict__ p_pack, const unsigned* __restrict__ p_sum,
                                                                  const unsigned* __restrict__ p_own, const unsigned* __restrict__ p_opp,
@@ -152,11 +136,11 @@ __global__ __launch_bounds__(BD_NT) void breakdown_reduce_kernel(const float* __
             above += s[i] >= t_pool;
         }
     }
-    sum = block_tree_sum(sum, bi);
-    members = block_tree_sum(members, bi);
-    opposite = block_tree_sum(opposite, bi);
-    above = block_tree_sum(above, bi);
-    ap = block_tree_sum(ap, bd);
+    sum = block_tree_sum<BD_NT>(sum, bi);
+    members = block_tree_sum<BD_NT>(members, bi);
+    opposite = block_tree_sum<BD_NT>(opposite, bi);
+    above = block_tree_sum<BD_NT>(above, bi);
+    ap = block_tree_sum<BD_NT>(ap, bd);
     if (threadIdx.x != 0) return;
     int64_t* row = out_counts + (size_t)k * BD_COLS;
     row[0] = sd ? 2 * members * opposite - sum : sum;

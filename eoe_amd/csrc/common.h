@@ -154,6 +154,42 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// The sum of one value per thread over a workgroup of NT threads in a fixed tree; the result in every thread.  buf: NT values in LDS.
+template <int NT, typename T>
+__device__ __forceinline__ T block_tree_sum(T v, T* buf) {
+    buf[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int h = NT / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) buf[threadIdx.x] += buf[threadIdx.x + h];
+        __syncthreads();
+    }
+    const T total = buf[0];
+    __syncthreads();                                         // buf is written again by the next sum
+    return total;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// fp32 bit images
+// ---------------------------------------------------------------------------------------------------
+// a NaN or an infinity
+__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
+// ascending unsigned order = ascending float order; -0.0 and 0.0 share an image
+__device__ __forceinline__ unsigned ordered_bits(float s) {
+    unsigned b = __float_as_uint(s);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float from_ordered_bits(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 
 // buffer resource (raw, bounds-checked: an out-of-range offset reads 0)
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -224,3 +260,4 @@ __device__ __forceinline__ void xcd_halves(int r, int total, int tiles_n, bool o
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline constexpr size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }      // scratch regions: a = 16 or 256

@@ -26,9 +26,8 @@ namespace {
 constexpr int CV_NT = 256;                     // count pass: threads per workgroup = scores per LDS tile
 constexpr int CV_SCAN = 1024;                  // compaction: places per chunk = threads of its one workgroup
 constexpr int CV_N_MAX = 1 << 20;
-constexpr size_t CV_ALIGN = 256;
 
-size_t plane_bytes(int n) { return ((size_t)n * 4 + CV_ALIGN - 1) / CV_ALIGN * CV_ALIGN; }
+size_t plane_bytes(int n) { return align_up((size_t)n * 4, 256); }
 
 __global__ __launch_bounds__(CV_NT) void curve_count_kernel(const float* __restrict__ s, const int64_t* __restrict__ labels, int64_t positive,
                                                             int n, int* __restrict__ flag, int* __restrict__ p_fps,

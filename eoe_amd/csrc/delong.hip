@@ -36,9 +36,8 @@ constexpr int DL_N_MAX = 1 << 20;              // the cap of breakdown.hip
 constexpr int DL_K_MAX = 8;
 constexpr int DL_TARGET_WGS = 2048;            // count pass: slices are added until the grid has about this many workgroups ...
 constexpr int DL_MAX_SLICES = 64;              // ... but never more than this
-constexpr size_t DL_ALIGN = 256;
 
-size_t order_bytes(int n) { return ((size_t)n * 4 + DL_ALIGN - 1) / DL_ALIGN * DL_ALIGN; }
+size_t order_bytes(int n) { return align_up((size_t)n * 4, 256); }
 int row_blocks(int n) { return cdiv(n, DL_NT) + 1; }                // cdiv(m, 256) + cdiv(n0, 256) <= cdiv(n, 256) + 1
 int pairs(int K) { return K * (K + 1) / 2; }
 int slices_for(int n, int K) {
@@ -125,20 +124,6 @@ __global__ __launch_bounds__(DL_NT) void delong_count_kernel(const float* __rest
     if (inside) atomicAdd(&cnt[(size_t)blockIdx.z * rows_cap + (size_t)b * DL_NT + threadIdx.x], 2u * gt + eq);
 }
 
-// the sum of one value per thread over the workgroup in a fixed tree; the result in every thread
-__device__ __forceinline__ long long block_tree_sum(long long v, long long* buf) {
-    buf[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int h = DL_NT / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) buf[threadIdx.x] += buf[threadIdx.x + h];
-        __syncthreads();
-    }
-    const long long total = buf[0];
-    __syncthreads();                                                   // buf is written again by the next sum
-    return total;
-}
-
 __global__ __launch_bounds__(DL_NT) void delong_reduce_kernel(const unsigned* __restrict__ cnt, int K, int rows_cap,
                                                               int64_t* __restrict__ out, const int64_t* __restrict__ out_sizes) {
     __shared__ long long buf[DL_NT];
@@ -160,8 +145,8 @@ __global__ __launch_bounds__(DL_NT) void delong_reduce_kernel(const unsigned* __
         prod += vk * vl;
         sum += vk;
     }
-    prod = block_tree_sum(prod, buf);
-    sum = block_tree_sum(sum, buf);
+    prod = block_tree_sum<DL_NT>(prod, buf);
+    sum = block_tree_sum<DL_NT>(sum, buf);
     if (threadIdx.x != 0) return;
     const int P = K * (K + 1) / 2;
     out[2 * K + side * P + blockIdx.x] = prod;

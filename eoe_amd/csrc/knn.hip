@@ -9,17 +9,14 @@
 //                 accumulate, bit for bit a k-ordered fmaf chain (no 16-bit rounding enters a ranking).  A = references, B = queries,
 //                 so a lane of the result holds ONE query and 16 references: the tile goes to LDS as [reference][query] with the
 //                 query contiguous, free of bank conflicts on the way in and on the way out.
-//   tile          256 threads = 4 waves as 2 x 2, a wave 64 references x 64 queries = 2 x 2 MFMA tiles = 64 accumulator registers;
-//                 k-step 32 (operand tiles [32][129] floats each, k-major: an MFMA operand read is 32 consecutive floats per half
-//                 wave; the odd stride spreads the transposing stores of the 16-byte global loads over the banks).  The next k-step's
-//                 global loads are issued in front of the MFMAs of this one.  A D that is no multiple of 32 is zero-filled in LDS;
-//                 nothing is read past column D of a row.
+//   tile          the 128 references x 128 queries x 32 tile layer of f32_tile.h (its workgroup shape, operand images of stride 129,
+//                 k order and accumulator map).  The next k-step's global loads are issued in front of the MFMAs of this one.
 //   LDS           65 536 B (the distance tile; the operand tiles, 33 024 B, alias it) + 1 024 B (the tile's reference norms and
 //                 flags) + k * 8 B * 256 lists (k <= 32) or * 128 lists (k > 32): 76.8 KB at k = 5 (2 workgroups = 2 waves per SIMD),
 //                 132 KB at k = 64 (1 wave per SIMD; the fp32 MFMA reaches its rate from one wave with four accumulators).
 //   select        a workgroup takes 128 queries and one chunk of 1 024 references (8 tiles).  After a tile, one thread (k > 32) or
 //                 two threads (each half of the tile's references) per query walk its distances in ascending reference order and keep
-//                 the k smallest keys seen, key = ordered_bits(d2) << 32 | reference index (topk.hip's order-preserving image), in a
+//                 the k smallest keys seen, key = ordered_bits(d2) << 32 | reference index (the order-preserving image topk.hip uses), in a
 //                 sorted list in LDS ([slot][thread]: lanes of a wave hit consecutive banks); the k-th key stays in a register, so a
 //                 candidate costs one compare unless it enters.  At the chunk's end the two lists of a query are merged and the k keys go
 //                 to scratch[nq][chunks][k] (an empty slot is all ones).
@@ -27,17 +24,16 @@
 //                 then index and distance from the key.  Wave 0 also adds up the row flags into counts.
 // Integer compares only once a distance is formed, no atomics, every scratch word that is read is written first: two runs give the
 // same bytes and a dirty scratch changes nothing.  Three launches on the caller's stream.
-#include "common.h"
+#include "f32_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace f32_tile;
 
-constexpr int KN_NT = 256;
-constexpr int KN_BM = 128;                     // queries per workgroup
-constexpr int KN_BN = 128;                     // references per tile
-constexpr int KN_BK = 32;                      // k-step
-constexpr int KN_LD = 129;                     // operand tile row stride (floats)
+constexpr int KN_NT = NT;
+constexpr int KN_BM = TILE;                    // queries per workgroup
+constexpr int KN_BN = TILE;                    // references per tile
+constexpr int KN_LD = LD_QUAD;                 // a 16-byte load holds four k of one row: transposing stores
 constexpr int KN_CHUNK = 1024;                 // references per workgroup
 constexpr int KN_K_MAX = 64;
 constexpr int KN_D_MAX = 2048;
@@ -45,7 +41,6 @@ constexpr int KN_NR_MAX = 1 << 24;
 constexpr unsigned long long KN_EMPTY = ~0ull;
 constexpr unsigned KN_INF_BITS = 0xFF800000u;  // ordered_bits(+inf): every eligible distance is at or below it
 
-__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 int knn_chunks(int nr) { return cdiv(nr, KN_CHUNK); }
 __host__ __device__ constexpr int knn_tpr(int k) { return k <= 32 ? 2 : 1; }           // selection threads per query
 size_t knn_lds_bytes(int k) { return (size_t)KN_BN * KN_BM * 4 + (size_t)k * KN_BM * knn_tpr(k) * 8; }
@@ -56,36 +51,12 @@ struct KnnScratch {                            // byte offsets into the caller's
 KnnScratch knn_layout(int nq, int nr, int k) {
     KnnScratch s;
     s.qn = 0;
-    s.rn = s.qn + align16((size_t)nq * 4);
-    s.qf = s.rn + align16((size_t)nr * 4);
-    s.rf = s.qf + align16((size_t)nq * 4);
-    s.keys = s.rf + align16((size_t)nr * 4);
-    s.total = s.keys + align16((size_t)nq * knn_chunks(nr) * k * 8) + 16;
+    s.rn = s.qn + align_up((size_t)nq * 4, 16);
+    s.qf = s.rn + align_up((size_t)nr * 4, 16);
+    s.rf = s.qf + align_up((size_t)nq * 4, 16);
+    s.keys = s.rf + align_up((size_t)nr * 4, 16);
+    s.total = s.keys + align_up((size_t)nq * knn_chunks(nr) * k * 8, 16) + 16;
     return s;
-}
-
-__device__ __forceinline__ unsigned ordered_bits(float s) {      // topk.hip: ascending unsigned order = ascending float order
-    unsigned b = __float_as_uint(s);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered_bits(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
-
-// row `row` of x, columns [k, k + 4): zero past column D and for a row past the set.  `vec`: base 16-byte aligned and ld % 4 == 0.
-__device__ __forceinline__ float4 load_quad(const float* __restrict__ x, int ld, int row, int nrows, int k, int D, bool vec) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < nrows && k < D) {
-        const float* p = x + (size_t)row * ld + k;
-        if (vec && k + 4 <= D) {
-            v = *reinterpret_cast<const float4*>(p);
-        } else {
-            v.x = p[0];
-            if (k + 1 < D) v.y = p[1];
-            if (k + 2 < D) v.z = p[2];
-            if (k + 3 < D) v.w = p[3];
-        }
-    }
-    return v;
 }
 
 // one wave per row of q (rows [0, nq)) and of r (rows [nq, nq + nr)): squared norm and the non-finite flag
@@ -99,14 +70,8 @@ __global__ __launch_bounds__(KN_NT) void knn_norm_kernel(const float* __restrict
     const int i = isq ? (int)row : (int)(row - nq);
     const float* p = isq ? q + (size_t)i * ldq : r + (size_t)i * ldr;
     float s = 0.f;
-    bool bad = false;
-    for (int c = lane; c < D; c += 64) {
-        const float v = p[c];
-        bad |= (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
-        s = fmaf(v, v, s);
-    }
+    const bool any = row_nonfinite(p, D, lane, [&](float v) { s = fmaf(v, v, s); });
     s = wave_sum(s);
-    const bool any = __ballot(bad) != 0ull;
     if (lane == 0) {
         (isq ? qn : rn)[i] = s;
         (isq ? qf : rf)[i] = any ? 1 : 0;
@@ -135,12 +100,12 @@ __global__ __launch_bounds__(KN_NT) void knn_tile_kernel(const float* __restrict
     __shared__ float rn_s[KN_BN];
     __shared__ int rok_s[KN_BN];
     float* stage = reinterpret_cast<float*>(kn_lds);                          // [KN_BN references][KN_BM queries]
-    float* As = stage;                                                        // [KN_BK][KN_LD] references, aliases the stage
-    float* Bs = stage + KN_BK * KN_LD;                                        // [KN_BK][KN_LD] queries
+    float* As = stage;                                                        // [BK][KN_LD] references, aliases the stage
+    float* Bs = stage + BK * KN_LD;                                           // [BK][KN_LD] queries
     unsigned long long* lists = reinterpret_cast<unsigned long long*>(kn_lds + (size_t)KN_BN * KN_BM * 4);
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = wave >> 1, wq = wave & 1;                                  // the wave's 64 references x 64 queries of the tile
+    const int t = threadIdx.x;
+    const Wave w = wave_coords();                                             // the wave's 64 references (A) x 64 queries (B) of the tile
     const int ch = (int)(blockIdx.x % (unsigned)chunks), qb = (int)(blockIdx.x / (unsigned)chunks);
     const int q0 = qb * KN_BM;
     const int tpr = knn_tpr(k), nsel = KN_BM * tpr, per = KN_BN / tpr;
@@ -154,26 +119,21 @@ __global__ __launch_bounds__(KN_NT) void knn_tile_kernel(const float* __restrict
     float qn[2];
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
-        const int qq = q0 + wq * 64 + qi * 32 + (lane & 31);
+        const int qq = q0 + b_row(w, qi);
         qn[qi] = qq < nq ? qnorm[qq] : 0.f;
     }
 
-    const int nkt = (D + KN_BK - 1) / KN_BK;
+    const int nkt = (D + BK - 1) / BK;
     for (int tile = 0; tile < KN_CHUNK / KN_BN; ++tile) {
         const int r0 = ch * KN_CHUNK + tile * KN_BN;
         if (r0 >= nr) break;                                                  // uniform over the workgroup
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+        Acc acc;
+        zero(acc);
         float4 ra[4], rb[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ra[j] = load_quad(r, ldr, r0 + lrow + 32 * j, nr, lk, D, vecr != 0);
-            rb[j] = load_quad(q, ldq, q0 + lrow + 32 * j, nq, lk, D, vecq != 0);
+        for (int j = 0; j < 4; ++j) {                                         // a row past its set reads as zeros
+            ra[j] = load_quad(r, ldr, r0 + lrow + 32 * j, lk, D, vecr != 0, r0 + lrow + 32 * j < nr);
+            rb[j] = load_quad(q, ldq, q0 + lrow + 32 * j, lk, D, vecq != 0, q0 + lrow + 32 * j < nq);
         }
         for (int kt = 0; kt < nkt; ++kt) {
             __syncthreads();                                                  // the last reads of the operand tiles and of the stage are done
@@ -184,42 +144,28 @@ __global__ __launch_bounds__(KN_NT) void knn_tile_kernel(const float* __restrict
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int row = lrow + 32 * j;
-                As[(lk + 0) * KN_LD + row] = ra[j].x; As[(lk + 1) * KN_LD + row] = ra[j].y;
-                As[(lk + 2) * KN_LD + row] = ra[j].z; As[(lk + 3) * KN_LD + row] = ra[j].w;
-                Bs[(lk + 0) * KN_LD + row] = rb[j].x; Bs[(lk + 1) * KN_LD + row] = rb[j].y;
-                Bs[(lk + 2) * KN_LD + row] = rb[j].z; Bs[(lk + 3) * KN_LD + row] = rb[j].w;
+                store_quad_t<KN_LD>(As, lk, lrow + 32 * j, ra[j]);
+                store_quad_t<KN_LD>(Bs, lk, lrow + 32 * j, rb[j]);
             }
             __syncthreads();
             if (kt + 1 < nkt) {
-                const int kk = (kt + 1) * KN_BK + lk;
+                const int kk = (kt + 1) * BK + lk;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    ra[j] = load_quad(r, ldr, r0 + lrow + 32 * j, nr, kk, D, vecr != 0);
-                    rb[j] = load_quad(q, ldq, q0 + lrow + 32 * j, nq, kk, D, vecq != 0);
+                    ra[j] = load_quad(r, ldr, r0 + lrow + 32 * j, kk, D, vecr != 0, r0 + lrow + 32 * j < nr);
+                    rb[j] = load_quad(q, ldq, q0 + lrow + 32 * j, kk, D, vecq != 0, q0 + lrow + 32 * j < nq);
                 }
             }
-            const float* ap = As + (lane >> 5) * KN_LD + wr * 64 + (lane & 31);
-            const float* bp = Bs + (lane >> 5) * KN_LD + wq * 64 + (lane & 31);
-#pragma unroll
-            for (int ks = 0; ks < KN_BK; ks += 2) {
-                const float a0 = ap[ks * KN_LD], a1 = ap[ks * KN_LD + 32];
-                const float b0 = bp[ks * KN_LD], b1 = bp[ks * KN_LD + 32];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
+            mma_step<KN_LD>(As, Bs, acc, w);
         }
         __syncthreads();                                                      // every wave has read its operands: the stage may take their place
 #pragma unroll
-        for (int ri = 0; ri < 2; ++ri)
+        for (int ri = 0; ri < 2; ++ri)                                        // acc_walk's order, spelled out: see the note at acc_walk
 #pragma unroll
             for (int qi = 0; qi < 2; ++qi)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int rl = wr * 64 + ri * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                    const int ql = wq * 64 + qi * 32 + (lane & 31);
+                    const int rl = a_row(w, ri, e), ql = b_row(w, qi);
                     stage[rl * KN_BM + ql] = fmaf(-2.f, acc[ri][qi][e], qn[qi] + rn_s[rl]);
                 }
         __syncthreads();
@@ -250,15 +196,6 @@ __global__ __launch_bounds__(KN_NT) void knn_tile_kernel(const float* __restrict
             for (int s = 0; s < k; ++s) out[s] = mine[s * nsel];
         }
     }
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
 }
 
 // one wave per query: the k smallest of its chunks * k distinct keys, ascending; wave 0 adds up the flags

@@ -1,7 +1,7 @@
 // The Gaussian baseline in feature space: the moments of a set of fp32 feature vectors (mean, scatter matrix, the fourth moment that
 // Ledoit-Wolf shrinkage needs) and the squared Mahalanobis distance of query rows, d2 = |W (x - mean)|^2.  Both matrix products run on
-// v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate, bit for bit a k-ordered fmaf chain) with the tile shapes of knn.hip: 256 threads =
-// 4 waves as 2 x 2, a wave 64 x 64 = 2 x 2 MFMA tiles, k-step 32, k-major operand tiles in LDS, ragged edges zero-filled in LDS.
+// v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate, bit for bit a k-ordered fmaf chain) through the 128 x 128 x 32 tile layer of
+// f32_tile.h, which knn.hip uses too: its workgroup shape, k-major operand images, k order and accumulator map.
 //
 // eoe_feature_moments, six launches:
 //   flags         one wave per row: does it hold a NaN or an infinity.  Such a row is excluded from everything below.
@@ -13,9 +13,8 @@
 //                 butterfly sum; 0 for an excluded row.
 //   scatter       S = Z^T Z.  The reduction runs over the ROWS of x, so a k-major operand tile [32 rows][128 columns] is x as it lies
 //                 in memory: 16-byte loads go to LDS as 16-byte stores, z = x - mean formed on the way (no centred copy of x exists;
-//                 an excluded row, a row past the slice and a column past D are zeros).  Row stride 160 floats: the two half waves of
-//                 an MFMA operand read (k and k + 1) fall on the two halves of the 64 banks.  Only the 128 x 128 tiles on or above the
-//                 diagonal are computed, nt (nt + 1) / 2 of them with nt = ceil(D / 128); a diagonal tile stages one operand and reads
+//                 an excluded row, a row past the slice and a column past D are zeros): the image of row stride 160.  Only the
+//                 128 x 128 tiles on or above the diagonal are computed, nt (nt + 1) / 2 of them with nt = ceil(D / 128); a diagonal tile stages one operand and reads
 //                 it twice.  The rows are cut into `splits` slices, a pure function of (n, D): the count that brings tiles x splits
 //                 to 256 workgroups or just above, one per CU (26 at D = 512, 2 at D = 2048), never more than ceil(n / 32).  Each
 //                 (tile, split) workgroup writes its whole fp32 tile to scratch: 17 MB at D = 512, 18 MB at D = 2048, any n
@@ -28,7 +27,7 @@
 // eoe_mahalanobis_score, three launches:
 //   flags         as above, for the query rows.
 //   tiles         y = W (x - mean) for 128 queries x 128 rows of W per workgroup: A = W, B = the centred queries (formed while the tile
-//                 is staged), operand tiles [32][129] as in knn.hip.  A lane of the result holds ONE query and 16 rows of W: it squares
+//                 is staged), the images of row stride 129.  A lane of the result holds ONE query and 16 rows of W: it squares
 //                 and adds them in register order (an fmaf chain), adds the other half wave's sum and the other wave's through LDS,
 //                 and writes one fp32 partial per (query, column tile) to scratch.  y is never stored.
 //                 Partials rather than one workgroup per query tile: at nq = 10 000, D = P = 512 that is 79 x 4 = 316 workgroups on
@@ -38,25 +37,23 @@
 //   sum           a thread per query adds its partials in ascending order; NaN for a flagged query; workgroup 0 counts the flags.
 //
 // No atomics, fixed orders, every scratch word that is read is written first: two runs give the same bytes under any scratch content.
-#include "common.h"
+#include "f32_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace f32_tile;
 
-constexpr int MH_NT = 256;
-constexpr int MH_TILE = 128;                   // columns of x (moments) / queries and rows of W (score) per workgroup
-constexpr int MH_BK = 32;                      // k-step
-constexpr int MH_LDM = 160;                    // moments operand tile row stride (floats): 16-byte rows, half waves 32 banks apart
-constexpr int MH_LDS = 129;                    // score operand tile row stride (knn.hip)
+constexpr int MH_NT = NT;
+constexpr int MH_TILE = TILE;                  // columns of x (moments) / queries and rows of W (score) per workgroup
+constexpr int MH_BK = BK;                      // k-step
+constexpr int MH_LDM = LD_ROWS;                // moments: x lies k-major in memory, 16-byte row stores
+constexpr int MH_LDS = LD_QUAD;                // score: a 16-byte load holds four k of one row, transposing stores
 constexpr int MH_D_MAX = 2048;
 constexpr int MH_N_MAX = 1 << 30;
 constexpr int MH_CS_ROWS = 256;                // rows per slice of the column sums ...
 constexpr int MH_CS_MAX = 512;                 // ... unless that makes more slices than this
 constexpr int MH_CUS = 256;
 constexpr int MH_SUB = 32;                     // the finish kernel's block edge
-
-__host__ __device__ constexpr size_t mh_align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 int mh_tiles_1d(int D) { return cdiv(D, MH_TILE); }
 int mh_upper_tiles(int D) { const int nt = mh_tiles_1d(D); return nt * (nt + 1) / 2; }
@@ -94,10 +91,10 @@ MomScratch mom_layout(int n, int D) {
     const long long parts = T * ksteps < MH_CUS - 1 + T ? T * ksteps : MH_CUS - 1 + T;
     MomScratch s;
     s.flag = 0;
-    s.rq = s.flag + mh_align16((size_t)n * 4);
-    s.pcnt = s.rq + mh_align16((size_t)n * 4);
-    s.psum = s.pcnt + mh_align16((size_t)slices * 4);
-    s.part = s.psum + mh_align16((size_t)slices * D * 8);
+    s.rq = s.flag + align_up((size_t)n * 4, 16);
+    s.pcnt = s.rq + align_up((size_t)n * 4, 16);
+    s.psum = s.pcnt + align_up((size_t)slices * 4, 16);
+    s.part = s.psum + align_up((size_t)slices * D * 8, 16);
     s.total = s.part + (size_t)parts * MH_TILE * MH_TILE * 4 + 16;
     return s;
 }
@@ -107,37 +104,9 @@ struct ScoreScratch {
 ScoreScratch score_layout(int nq, int P) {
     ScoreScratch s;
     s.flag = 0;
-    s.part = s.flag + mh_align16((size_t)nq * 4);
-    s.total = s.part + mh_align16((size_t)nq * cdiv(P, MH_TILE) * 4) + 16;
+    s.part = s.flag + align_up((size_t)nq * 4, 16);
+    s.total = s.part + align_up((size_t)nq * cdiv(P, MH_TILE) * 4, 16) + 16;
     return s;
-}
-
-__device__ __forceinline__ bool mh_nonfinite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
-
-// row `row` of x, columns [k, k + 4): zero past column D.  `vec`: base 16-byte aligned and ld % 4 == 0.  The caller has checked the row.
-__device__ __forceinline__ float4 mh_load_quad(const float* __restrict__ x, int ld, int row, int k, int D, bool vec) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < D) {
-        const float* p = x + (size_t)row * ld + k;
-        if (vec && k + 4 <= D) {
-            v = *reinterpret_cast<const float4*>(p);
-        } else {
-            v.x = p[0];
-            if (k + 1 < D) v.y = p[1];
-            if (k + 2 < D) v.z = p[2];
-            if (k + 3 < D) v.w = p[3];
-        }
-    }
-    return v;
-}
-// entries [k, k + 4) of a contiguous fp32 vector of length D, zero past it (element loads: the vector may start anywhere)
-__device__ __forceinline__ float4 mh_vec_quad(const float* __restrict__ m, int k, int D) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < D) v.x = m[k];
-    if (k + 1 < D) v.y = m[k + 1];
-    if (k + 2 < D) v.z = m[k + 2];
-    if (k + 3 < D) v.w = m[k + 3];
-    return v;
 }
 
 // one wave per row: 1 for a row that holds a NaN or an infinity
@@ -145,10 +114,7 @@ __global__ __launch_bounds__(MH_NT) void mh_flag_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * (MH_NT / 64) + (threadIdx.x >> 6);
     if (row >= n) return;
-    const float* p = x + (size_t)row * ld;
-    bool bad = false;
-    for (int c = lane; c < D; c += 64) bad |= mh_nonfinite(p[c]);
-    const bool any = __ballot(bad) != 0ull;
+    const bool any = row_nonfinite(x + (size_t)row * ld, D, lane, [](float) {});
     if (lane == 0) flag[row] = any ? 1 : 0;
 }
 
@@ -211,27 +177,21 @@ __global__ __launch_bounds__(MH_NT) void mh_scatter_kernel(const float* __restri
                                                            float* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) float As[MH_BK * MH_LDM];
     __shared__ __attribute__((aligned(16))) float Bs[MH_BK * MH_LDM];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = wave >> 1, wq = wave & 1;
+    const int t = threadIdx.x;
+    const Wave w = wave_coords();
     const int tile = (int)(blockIdx.x / (unsigned)splits), sp = (int)(blockIdx.x % (unsigned)splits);
     int ta, tb;
     mh_tile_pair(tile, nt, ta, tb);
     const bool diag = ta == tb;
     const int ca = ta * MH_TILE + (t & 31) * 4, cb = tb * MH_TILE + (t & 31) * 4;   // this thread's column quad of either operand
     const int lrow = t >> 5;                                                        // its first row of a k-step (then + 8)
-    const float4 ma = mh_vec_quad(mean, ca, D), mb = mh_vec_quad(mean, cb, D);
+    const float4 ma = vec_quad(mean, ca, D), mb = vec_quad(mean, cb, D);
     const long long row0 = (long long)sp * rows_per;
     const long long row1 = row0 + rows_per < n ? row0 + rows_per : n;
     const int nkt = row1 > row0 ? (int)((row1 - row0 + MH_BK - 1) / MH_BK) : 0;
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
+    Acc acc;
+    zero(acc);
     float4 ra[4], rb[4];
     auto fetch = [&](int kt) {
 #pragma unroll
@@ -240,11 +200,11 @@ __global__ __launch_bounds__(MH_NT) void mh_scatter_kernel(const float* __restri
             ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
             rb[j] = ra[j];
             if (r < row1 && !flag[r]) {                                       // past column D both x and the mean read as 0
-                const float4 v = mh_load_quad(x, ld, (int)r, ca, D, vec != 0);
+                const float4 v = load_quad(x, ld, (int)r, ca, D, vec != 0);
                 ra[j] = make_float4(v.x - ma.x, v.y - ma.y, v.z - ma.z, v.w - ma.w);
                 if (!diag) {
-                    const float4 w = mh_load_quad(x, ld, (int)r, cb, D, vec != 0);
-                    rb[j] = make_float4(w.x - mb.x, w.y - mb.y, w.z - mb.z, w.w - mb.w);
+                    const float4 u = load_quad(x, ld, (int)r, cb, D, vec != 0);
+                    rb[j] = make_float4(u.x - mb.x, u.y - mb.y, u.z - mb.z, u.w - mb.w);
                 }
             }
         }
@@ -261,29 +221,10 @@ __global__ __launch_bounds__(MH_NT) void mh_scatter_kernel(const float* __restri
         }
         __syncthreads();
         if (kt + 1 < nkt) fetch(kt + 1);
-        const float* ap = As + (lane >> 5) * MH_LDM + wr * 64 + (lane & 31);
-        const float* bp = bsrc + (lane >> 5) * MH_LDM + wq * 64 + (lane & 31);
-#pragma unroll
-        for (int ks = 0; ks < MH_BK; ks += 2) {
-            const float a0 = ap[ks * MH_LDM], a1 = ap[ks * MH_LDM + 32];
-            const float b0 = bp[ks * MH_LDM], b1 = bp[ks * MH_LDM + 32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        mma_step<MH_LDM>(As, bsrc, acc, w);
     }
     float* out = part + (size_t)blockIdx.x * (MH_TILE * MH_TILE);            // [tile][split][128 a][128 b], the whole tile
-#pragma unroll
-    for (int ri = 0; ri < 2; ++ri)
-#pragma unroll
-        for (int qi = 0; qi < 2; ++qi)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int al = wr * 64 + ri * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                const int bl = wq * 64 + qi * 32 + (lane & 31);
-                out[al * MH_TILE + bl] = acc[ri][qi][e];
-            }
+    acc_walk(acc, w, [&](int al, int bl, float v) { out[al * MH_TILE + bl] = v; });
 }
 
 // blocks [0, tiles * 16): a 32 x 32 block of an upper tile; the last block: m4
@@ -299,13 +240,8 @@ __global__ __launch_bounds__(MH_NT) void mh_finish_kernel(int n, int D, int nt, 
             const double q = (double)rq[i];
             acc += q * q;
         }
-        red[t] = acc;
-        __syncthreads();
-        for (int o = MH_NT / 2; o > 0; o >>= 1) {
-            if (t < o) red[t] += red[t + o];
-            __syncthreads();
-        }
-        if (t == 0) m4[0] = red[0];
+        acc = block_tree_sum<MH_NT>(acc, red);
+        if (t == 0) m4[0] = acc;
         return;
     }
     const int tile = blockIdx.x / (PER * PER), sub = blockIdx.x % (PER * PER);
@@ -340,8 +276,8 @@ __global__ __launch_bounds__(MH_NT) void mh_score_kernel(const float* __restrict
     __shared__ float As[MH_BK * MH_LDS];                                      // [k][row of W]
     __shared__ float Bs[MH_BK * MH_LDS];                                      // [k][query]
     __shared__ float red[MH_TILE];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = wave >> 1, wq = wave & 1;                                  // the wave's 64 rows of W x 64 queries
+    const int t = threadIdx.x;
+    const Wave w = wave_coords();                                             // the wave's 64 rows of W (A) x 64 queries (B)
     const int pt = (int)(blockIdx.x % (unsigned)ptiles), qb = (int)(blockIdx.x / (unsigned)ptiles);
     const int q0 = qb * MH_TILE, p0 = pt * MH_TILE;
     const int lk = (t & 7) * 4, lrow = t >> 3;                                // loads: k quad and first row (then + 32)
@@ -349,26 +285,20 @@ __global__ __launch_bounds__(MH_NT) void mh_score_kernel(const float* __restrict
     if (lower && p0 + MH_TILE < D) kend = p0 + MH_TILE;                       // W[j, k] == 0 for k > j: nothing past the tile's last row
     const int nkt = (kend + MH_BK - 1) / MH_BK;
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
+    Acc acc;
+    zero(acc);
     float4 ra[4], rb[4];
     auto fetch = [&](int kt) {
         const int kk = kt * MH_BK + lk;
-        const float4 m = mh_vec_quad(mean, kk, D);
+        const float4 m = vec_quad(mean, kk, D);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int wrow = p0 + lrow + 32 * j, qrow = q0 + lrow + 32 * j;
             ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
             rb[j] = ra[j];
-            if (wrow < P) ra[j] = mh_load_quad(W, ldw, wrow, kk, D, vecw != 0);
+            if (wrow < P) ra[j] = load_quad(W, ldw, wrow, kk, D, vecw != 0);
             if (qrow < nq) {
-                const float4 v = mh_load_quad(x, ldx, qrow, kk, D, vecx != 0);
+                const float4 v = load_quad(x, ldx, qrow, kk, D, vecx != 0);
                 rb[j] = make_float4(v.x - m.x, v.y - m.y, v.z - m.z, v.w - m.w);       // past column D both are 0
             }
         }
@@ -378,27 +308,16 @@ __global__ __launch_bounds__(MH_NT) void mh_score_kernel(const float* __restrict
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int row = lrow + 32 * j;
-            As[(lk + 0) * MH_LDS + row] = ra[j].x; As[(lk + 1) * MH_LDS + row] = ra[j].y;
-            As[(lk + 2) * MH_LDS + row] = ra[j].z; As[(lk + 3) * MH_LDS + row] = ra[j].w;
-            Bs[(lk + 0) * MH_LDS + row] = rb[j].x; Bs[(lk + 1) * MH_LDS + row] = rb[j].y;
-            Bs[(lk + 2) * MH_LDS + row] = rb[j].z; Bs[(lk + 3) * MH_LDS + row] = rb[j].w;
+            store_quad_t<MH_LDS>(As, lk, lrow + 32 * j, ra[j]);
+            store_quad_t<MH_LDS>(Bs, lk, lrow + 32 * j, rb[j]);
         }
         __syncthreads();
         if (kt + 1 < nkt) fetch(kt + 1);
-        const float* ap = As + (lane >> 5) * MH_LDS + wr * 64 + (lane & 31);
-        const float* bp = Bs + (lane >> 5) * MH_LDS + wq * 64 + (lane & 31);
-#pragma unroll
-        for (int ks = 0; ks < MH_BK; ks += 2) {
-            const float a0 = ap[ks * MH_LDS], a1 = ap[ks * MH_LDS + 32];
-            const float b0 = bp[ks * MH_LDS], b1 = bp[ks * MH_LDS + 32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        mma_step<MH_LDS>(As, Bs, acc, w);
     }
-    // a lane holds query wq * 64 + qi * 32 + (lane & 31) and 2 x 16 rows of W: square and add, then the other half wave, then the other wave
+    // a lane holds query b_row(w, qi) and 2 x 16 rows of W: square and add in register order (qi outer; ri, e inner: part of the
+    // result, so no acc_walk here), then the other half wave, then the other wave
+    const int lane = w.lane, wr = w.wa;
     float s[2];
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
@@ -410,14 +329,14 @@ __global__ __launch_bounds__(MH_NT) void mh_score_kernel(const float* __restrict
         s[qi] = v + __shfl_xor(v, 32, 64);
     }
     if (wr == 1 && lane < 32) {
-        red[wq * 64 + lane] = s[0];
-        red[wq * 64 + 32 + lane] = s[1];
+        red[b_row(w, 0)] = s[0];
+        red[b_row(w, 1)] = s[1];
     }
     __syncthreads();
     if (wr == 0 && lane < 32) {
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi) {
-            const int ql = wq * 64 + qi * 32 + lane;
+            const int ql = b_row(w, qi);
             if (q0 + ql < nq) part[(size_t)(q0 + ql) * ptiles + pt] = s[qi] + red[ql];
         }
     }
@@ -437,13 +356,8 @@ __global__ __launch_bounds__(MH_NT) void mh_score_sum_kernel(int nq, int ptiles,
     if (blockIdx.x == 0) {
         int c = 0;
         for (long long i = t; i < nq; i += MH_NT) c += flag[i];
-        red[t] = c;
-        __syncthreads();
-        for (int o = MH_NT / 2; o > 0; o >>= 1) {
-            if (t < o) red[t] += red[t + o];
-            __syncthreads();
-        }
-        if (t == 0) count[0] = red[0];
+        c = block_tree_sum<MH_NT>(c, red);
+        if (t == 0) count[0] = c;
     }
 }
 

@@ -2,7 +2,7 @@
 // reference ranks OE individuals this way in `Tree.scores_best` / `imsave_best`, and leaves the test scores to a per-sample JSON the
 // user sorts by hand).  Four lists: (group 0, group 1) x (most, least); list l = 2 * group + end.
 //
-//   key           every member of a group gets one 52-bit integer per end: the order-preserving 32-bit image of its score (-0.0 folded
+//   key           every member of a group gets one 52-bit integer per end: the order-preserving 32-bit image of its score (ordered_bits: -0.0 folded
 //                 into 0.0; the image complemented for the "most" end) above its 20-bit position.  Keys of one list are distinct, and
 //                 ascending key order is the list's order -- descending (most) or ascending (least) by score, equal scores by
 //                 ascending position: what np.argsort(-s, kind="stable") and np.argsort(s, kind="stable") give.  A list is the
@@ -50,12 +50,6 @@ constexpr size_t TK_SCRATCH_BYTES = TK_OFF_KEYS + (size_t)TK_LISTS * TK_K_MAX * 
 
 int topk_grid(int n) { const int g = cdiv(n, TK_NT * 4); return g < TK_MAX_GRID ? g : TK_MAX_GRID; }
 
-// ascending unsigned order = ascending float order; -0.0 and 0.0 share an image
-__device__ __forceinline__ unsigned ordered_bits(float s) {
-    unsigned b = __float_as_uint(s);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 __device__ __forceinline__ unsigned long long make_key(unsigned u, int end, unsigned i) {
     return ((unsigned long long)(end == 0 ? ~u : u) << TK_IDX_BITS) | i;
 }
@@ -140,7 +134,7 @@ __global__ __launch_bounds__(TK_NT) void topk_pass_kernel(const float* __restric
         if (g < 0) continue;
         const float x = s[i];
         const unsigned u = ordered_bits(x);
-        if (P == 0 && (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u) atomicAdd(&s_nf, 1u);
+        if (P == 0 && ::nonfinite(x)) atomicAdd(&s_nf, 1u);          // the function of common.h, not the counter
 #pragma unroll
         for (int end = 0; end < 2; ++end) {
             const int l = 2 * g + end;
