@@ -27,9 +27,10 @@ from . import explain                    # noqa: F401,E402
 from .explain import input_gradient, saliency, overlay, attention_rollout  # noqa: F401
 from .metrics import Breakdown, class_breakdown  # noqa: F401
 from .metrics import AucTest, delong     # noqa: F401
+from .metrics import Bootstrap, bootstrap  # noqa: F401
 
 __all__ = ["set_compute_dtype", "compute_dtype", "hsc_loss", "hsc_score", "bce_loss", "bce_score", "linear",
            "FusedAdam", "FusedSGD", "GraphedStep", "set_parity_mode", "parity_mode", "set_grad_scale", "grad_scale",
            "default_grad_scale", "fit_statistics", "gcn_normalize", "GlobalContrastNormalization", "GcnNormalize", "OEPool", "run_evolution",
            "image_grid", "explain", "input_gradient", "saliency", "overlay", "attention_rollout",
-           "Breakdown", "class_breakdown", "AucTest", "delong"]
+           "Breakdown", "class_breakdown", "AucTest", "delong", "Bootstrap", "bootstrap"]

@@ -239,6 +239,9 @@ SIGNATURES = {
     "eoe_delong_scratch_bytes": [C.c_int, C.c_int],
     "eoe_delong_slices": [C.c_int, C.c_int],
     "eoe_delong_counts": [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp],
+    "eoe_bootstrap_scratch_bytes": [C.c_int, C.c_int, C.c_int],
+    "eoe_bootstrap_counts": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
+    "eoe_bootstrap_draws": [_vp, C.c_int, C.c_int, C.c_uint64, _vp, _vp, _vp],
     "eoe_feature_knn_scratch_bytes": [C.c_int] * 4,
     "eoe_feature_knn": [_vp, C.c_int, _vp, C.c_int] + [C.c_int] * 4 + [_vp] * 5,
     "eoe_feature_moments_scratch_bytes": [C.c_int] * 2,
@@ -314,6 +317,7 @@ SIGNATURES = {
 _RESTYPES = {"eoe_last_error": C.c_char_p, "eoe_conv_f32_wgrad_workspace": _sz, "eoe_rank_curves_scratch_bytes": _sz,
              "eoe_score_hist_scratch_bytes": _sz, "eoe_score_extremes_scratch_bytes": _sz,
              "eoe_class_breakdown_scratch_bytes": _sz, "eoe_delong_scratch_bytes": _sz,
+             "eoe_bootstrap_scratch_bytes": _sz,
              "eoe_feature_knn_scratch_bytes": _sz, "eoe_feature_moments_scratch_bytes": _sz,
              "eoe_mahalanobis_score_scratch_bytes": _sz}
 

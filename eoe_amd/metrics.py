@@ -21,7 +21,11 @@ integer pair counts, one workgroup per class) for GPU tensors, sorts for host ar
 How much of a difference between two AUCs is test-set sampling noise -- DeLong's confidence interval of an AUC and the paired test of
 K models scored on the same samples, which neither the reference nor sklearn has -- is `delong` / `AucTest`: `eoe_delong_counts`
 (per sample the doubled count of opposite-label samples it beats or ties, then their sums and cross sums: exact integers) for GPU
-tensors, `searchsorted` for host arrays; the numerators in Python integers and one division per entry on the host."""
+tensors, `searchsorted` for host arrays; the numerators in Python integers and one division per entry on the host.
+
+What the other two numbers next to every AUC are worth -- the average precision and the FPR at a TPR level, for which there is no
+DeLong -- is `bootstrap` / `Bootstrap`: a stratified, paired bootstrap whose draws are stated exactly (Philox4x32-10 counters), every
+replicate resampled and counted by `eoe_bootstrap_counts` for GPU tensors and by `bootstrap_np` (the same integers) for host arrays."""
 from typing import Optional
 
 import numpy as np
@@ -1005,3 +1009,315 @@ def delong(labels, scores) -> Optional[AucTest]:
     if m == 0 or n0 == 0:
         return None
     return AucTest(t_pos, t_neg, A, B, m, n0)
+
+
+# ------------------------------------------------------------------------------------------------------ bootstrap
+BOOTSTRAP_MAX_N = DELONG_MAX_N            # eoe_bootstrap_counts
+BOOTSTRAP_MAX_COLUMNS = DELONG_MAX_COLUMNS
+BOOTSTRAP_MAX_REPLICATES = 1 << 16
+BOOTSTRAP_CHUNK = 16384                   # sorted positions a workgroup of the replicate pass counts in LDS at a time (EOE_BOOTSTRAP_CHUNK)
+BOOTSTRAP_STATS = ("auc", "ap", "fpr")
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32(counter, key) -> np.ndarray:
+    """Philox4x32-10 (Salmon, Moraes, Dror & Shaw 2011): `counter` [..., 4] and `key` [..., 2] as unsigned 32-bit words (the shapes
+    broadcast over the leading axes) -> uint32 [..., 4]"""
+    c = np.asarray(counter, dtype=np.uint64) & 0xFFFFFFFF
+    k = np.asarray(key, dtype=np.uint64) & 0xFFFFFFFF
+    lead = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], lead).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], lead).copy() for i in range(2))
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2           # 32 x 32 bits: no overflow in 64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & mask, (k1 + np.uint64(_PHILOX_W1)) & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _bootstrap_positions(size: int, reps: np.ndarray, stratum: int, seed: int) -> np.ndarray:
+    """int64 [len(reps), size]: the positions within a stratum of `size` samples that the replicates `reps` draw"""
+    calls = (size + 3) // 4
+    counter = np.zeros((reps.size, calls, 4), np.uint64)
+    counter[..., 0] = np.arange(calls, dtype=np.uint64)[None, :]
+    counter[..., 1] = reps.astype(np.uint64)[:, None]
+    counter[..., 2] = stratum
+    words = philox4x32(counter, np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], np.uint64))
+    words = words.reshape(reps.size, calls * 4)[:, :size].astype(np.uint64)       # the unused words of the last call are dropped
+    return ((words * np.uint64(size)) >> np.uint64(32)).astype(np.int64)
+
+
+def _check_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"a bootstrap seed must be an integer in [0, 2^64), not {seed!r}")
+    return int(seed)
+
+
+def _bootstrap_used_counts(m: int, n0: int, reps: np.ndarray, seed: int) -> np.ndarray:
+    """int64 [len(reps), m + n0]: per replicate the multiplicity of every used sample, positives first, each stratum in index order"""
+    N, R = m + n0, reps.size
+    rows = np.arange(R, dtype=np.int64)[:, None] * N
+    hit = np.concatenate([(rows + _bootstrap_positions(m, reps, 1, seed)).ravel(), (rows + m + _bootstrap_positions(n0, reps, 0, seed)).ravel()])
+    return np.bincount(hit, minlength=R * N).reshape(R, N)
+
+
+def bootstrap_multiplicities_np(labels, b: int, seed: int = 0) -> np.ndarray:
+    """int32 [n]: how often replicate `b` of the stratified bootstrap holds each sample -- m draws with replacement among the m samples
+    with label 1 and n0 among the n0 with label 0, each stratum numbered in ascending sample index; 0 for every other label.  Draws
+    4j .. 4j+3 of a (replicate, stratum) are the words of `philox4x32((j, b, stratum, 0), (seed & 0xffffffff, seed >> 32))`, stratum 0
+    for the negatives and 1 for the positives; a word w selects position (w * size) >> 32."""
+    y = np.asarray(_to_host(labels)).ravel()
+    seed = _check_seed(seed)
+    pos, neg = np.flatnonzero(y == 1), np.flatnonzero(y == 0)
+    out = np.zeros(y.size, np.int32)
+    if pos.size == 0 and neg.size == 0:
+        return out
+    c = _bootstrap_used_counts(pos.size, neg.size, np.array([int(b)], np.int64), seed)[0]
+    out[pos], out[neg] = c[:pos.size], c[pos.size:]
+    return out
+
+
+def _check_bootstrap_shape(n: int, K: int, n_labels: int, B):
+    if K < 1 or K > BOOTSTRAP_MAX_COLUMNS:
+        raise ValueError(f"a bootstrap takes between 1 and {BOOTSTRAP_MAX_COLUMNS} score columns, not {K}")
+    if n_labels != n:
+        raise ValueError(f"a bootstrap needs as many labels as scores per column, not {n_labels} and {n}")
+    if n < 2 or n > BOOTSTRAP_MAX_N:
+        raise ValueError(f"a bootstrap takes between 2 and {BOOTSTRAP_MAX_N} samples, not {n}")
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or B < 1 or B > BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"a bootstrap takes between 1 and {BOOTSTRAP_MAX_REPLICATES} replicates, not {B!r}")
+
+
+def _check_tpr(tpr) -> float:
+    if isinstance(tpr, bool) or not isinstance(tpr, (int, float, np.integer, np.floating)) or not 0.0 < float(tpr) <= 1.0:
+        raise ValueError(f"tpr must be in (0, 1], not {tpr!r}")
+    return float(tpr)
+
+
+def bootstrap_np(labels, scores, replicates: int = 2000, seed: int = 0, tpr: float = 0.95):
+    """The NumPy statement of the stratified, paired bootstrap (`bootstrap`): (u2 int64 [K, B + 1], fps int64 [K, B + 1], ap float64
+    [K, B + 1], m, n0) for labels [n] and scores [n] or [K, n].  Column b < B belongs to replicate b, column B to the full sample
+    (every multiplicity 1).  With c the multiplicities of `bootstrap_multiplicities_np` (shared by the K columns):
+
+      u2    sum over (positive i, negative j) of c[i] c[j] (2 [s_i > s_j] + [s_i == s_j]); the replicate's AUC is u2 / (2 m n0)
+      fps   the weighted negatives at or above the score at place `place_for_tpr(tpr, m)` of the resampled positives in descending
+            order; the FPR at that TPR is fps / n0
+      ap    sklearn's `average_precision_score` of the resample: over the distinct scores in descending order
+            sum (tps_g - tps_{g-1}) / m * (tps_g / (tps_g + fps_g)) with the weighted cumulative counts
+
+    from one stable sort per column, a `bincount` per replicate and `cumsum`s over the groups of equal scores.  float32 scores are
+    compared as float32, anything else as float64; -0.0 equals 0.0 and the infinities are ordinary values.  ValueError for a NaN
+    among the used scores.  Without a positive or a negative the tables are zeros."""
+    y = np.asarray(_to_host(labels)).ravel()
+    s = np.asarray(_to_host(scores))
+    s = s.reshape(1, -1) if s.ndim <= 1 else s.reshape(s.shape[0], -1)
+    if s.dtype != np.float32:
+        s = s.astype(np.float64)
+    K, n = s.shape
+    B, seed, tpr = replicates, _check_seed(seed), _check_tpr(tpr)
+    _check_bootstrap_shape(n, K, y.size, B)
+    B = int(B)
+    pos, neg = np.flatnonzero(y == 1), np.flatnonzero(y == 0)
+    m, n0 = int(pos.size), int(neg.size)
+    N = m + n0
+    u2, fps, ap = np.zeros((K, B + 1), np.int64), np.zeros((K, B + 1), np.int64), np.zeros((K, B + 1), np.float64)
+    used = np.concatenate([pos, neg])
+    if np.isnan(s[:, used]).any():
+        raise ValueError("scores contain NaN")
+    if m == 0 or n0 == 0:
+        return u2, fps, ap, m, n0
+    place = place_for_tpr(tpr, m)
+    cols = []
+    for k in range(K):
+        su = s[k, used]
+        perm = np.argsort(su, kind="stable")
+        ss = su[perm]
+        starts = np.flatnonzero(np.concatenate([[True], ss[1:] != ss[:-1]]))
+        cols.append((perm, starts, (perm < m).astype(np.int64)))
+    step = max(1, (1 << 21) // N)
+    for b0 in range(0, B + 1, step):
+        reps = np.arange(b0, min(b0 + step, B + 1), dtype=np.int64)
+        full = reps[-1] == B
+        c = _bootstrap_used_counts(m, n0, reps[:-1] if full else reps, seed)
+        if full:
+            c = np.concatenate([c, np.ones((1, N), np.int64)])
+        sl = slice(b0, b0 + reps.size)
+        for k, (perm, starts, is_pos) in enumerate(cols):
+            cs = c[:, perm]
+            posw = np.add.reduceat(cs * is_pos, starts, axis=1)                   # [R, groups], ascending score
+            negw = np.add.reduceat(cs * (1 - is_pos), starts, axis=1)
+            p_lt, n_lt = np.cumsum(posw, axis=1) - posw, np.cumsum(negw, axis=1) - negw
+            u2[k, sl] = (posw * (2 * n_lt + negw)).sum(axis=1)
+            tps, fpc = m - p_lt, n0 - n_lt                                        # the descending curve's counts at each group
+            at = (tps >= place).sum(axis=1) - 1                                   # tps falls along the groups: the last one that holds the place
+            fps[k, sl] = fpc[np.arange(reps.size), at]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                term = np.where(posw > 0, (posw / m) * (tps / (tps + fpc).astype(np.float64)), 0.0)
+            ap[k, sl] = term[:, ::-1].sum(axis=1)
+    return u2, fps, ap, m, n0
+
+
+def bootstrap_device(labels, scores, replicates: int = 2000, seed: int = 0, tpr: float = 0.95):
+    """`eoe_bootstrap_counts` on GPU-resident scores [n] or [K, n]: (u2 int64 [K, B + 1], fps int64 [K, B + 1], ap float64 [K, B + 1], m,
+    n0, the number of NaN scores) as host arrays and ints -- the raw tables of `bootstrap_np`, unchecked.  16-bit scores are compared
+    as float32.  `labels` may live on either device: at most one upload, one call (a memset and four launches) and ONE copy back."""
+    import torch
+    from ._lib import check, lib
+    if not _is_gpu_tensor(scores):
+        raise RuntimeError("bootstrap_device needs GPU scores (bootstrap takes host arrays as they are)")
+    sc = scores.detach()
+    sc = (sc.reshape(1, -1) if sc.dim() <= 1 else sc.reshape(sc.shape[0], -1)).contiguous().float()
+    K, n = int(sc.shape[0]), int(sc.shape[1])
+    la = torch.as_tensor(labels).reshape(-1).to(torch.int64).to(sc.device).contiguous()
+    seed, tpr = _check_seed(seed), _check_tpr(tpr)
+    _check_bootstrap_shape(n, K, la.numel(), replicates)
+    B = int(replicates)
+    T = K * (B + 1)
+    out = torch.empty(3 * T + 2, dtype=torch.int64, device=sc.device)      # u2 | fps | ap (float64 bits) | counts (three int32)
+    scratch = torch.empty(lib.eoe_bootstrap_scratch_bytes(n, K, B), dtype=torch.uint8, device=sc.device)
+    base = out.data_ptr()
+    with torch.cuda.device(sc.device):
+        check(lib.eoe_bootstrap_counts(sc.data_ptr(), la.data_ptr(), n, K, B, seed, tpr, base, base + 8 * T, base + 16 * T, base + 24 * T,
+                                       scratch.data_ptr(), torch.cuda.current_stream(sc.device).cuda_stream), "eoe_bootstrap_counts")
+    raw = out.cpu().numpy()
+    m, n0, bad = (int(x) for x in raw[3 * T:].view(np.int32)[:3])
+    return (raw[:T].reshape(K, B + 1).copy(), raw[T:2 * T].reshape(K, B + 1).copy(), raw[2 * T:3 * T].view(np.float64).reshape(K, B + 1).copy(),
+            m, n0, bad)
+
+
+def bootstrap_multiplicities_device(labels, b: int, seed: int = 0) -> np.ndarray:
+    """`eoe_bootstrap_draws`: `bootstrap_multiplicities_np` drawn on the device, for telling a difference in the draws from one in the
+    counting.  `labels`: a tensor on the GPU."""
+    import torch
+    from ._lib import check, lib
+    if not _is_gpu_tensor(labels):
+        raise RuntimeError("bootstrap_multiplicities_device needs GPU labels")
+    la = labels.detach().reshape(-1).to(torch.int64).contiguous()
+    n, seed = int(la.numel()), _check_seed(seed)
+    _check_bootstrap_shape(n, 1, n, 1)
+    if not 0 <= int(b) < BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"a replicate's number must be in [0, {BOOTSTRAP_MAX_REPLICATES}), not {b}")
+    out = torch.empty(n, dtype=torch.int32, device=la.device)
+    scratch = torch.empty(lib.eoe_bootstrap_scratch_bytes(n, 1, 1), dtype=torch.uint8, device=la.device)
+    with torch.cuda.device(la.device):
+        check(lib.eoe_bootstrap_draws(la.data_ptr(), n, int(b), seed, out.data_ptr(), scratch.data_ptr(),
+                                      torch.cuda.current_stream(la.device).cuda_stream), "eoe_bootstrap_draws")
+    return out.cpu().numpy()
+
+
+class Bootstrap:
+    """The stratified, paired bootstrap of K score columns over the same test samples: what an AUC, an average precision or an FPR at a
+    TPR level -- or a difference of two of them -- is worth on a test set of this size, without DeLong's normal approximation.
+
+      auc, ap, fpr [K]                    the statistics of the full sample;  tpr  the level of `fpr`
+      auc_reps, ap_reps, fpr_reps [K, B]  the replicates' (float64; one division per entry: u2 / (2 m n0), fps / n0)
+      n_pos, n_neg, replicates, seed
+      counts   the tables everything is divided from: {"u2", "fps": int64 [K, B + 1], "ap": float64 [K, B + 1]}, column B the full sample
+
+    Every replicate draws n_pos positives and n_neg negatives with replacement, and the K columns share the draws, so differences
+    between columns are paired.  `stat` is one of "auc", "ap", "fpr"."""
+
+    def __init__(self, u2, fps, ap, n_pos: int, n_neg: int, seed: int = 0, tpr: float = 0.95):
+        u2, fps, ap = np.asarray(u2, np.int64), np.asarray(fps, np.int64), np.asarray(ap, np.float64)
+        self.n_pos, self.n_neg, self.seed, self.tpr = int(n_pos), int(n_neg), int(seed), float(tpr)
+        if self.n_pos < 1 or self.n_neg < 1 or u2.ndim != 2 or u2.shape[1] < 2 or u2.shape != fps.shape or u2.shape != ap.shape:
+            raise ValueError("a bootstrap needs both classes and three tables of K x (B + 1) numbers")
+        self.counts = {"u2": u2, "fps": fps, "ap": ap}
+        self.replicates = u2.shape[1] - 1
+        auc, fpr = u2 / float(2 * self.n_pos * self.n_neg), fps / float(self.n_neg)         # int64 -> float64 is exact below 2^53
+        self.auc, self.ap, self.fpr = auc[:, -1].copy(), ap[:, -1].copy(), fpr[:, -1].copy()
+        self.auc_reps, self.ap_reps, self.fpr_reps = auc[:, :-1].copy(), ap[:, :-1].copy(), fpr[:, :-1].copy()
+
+    def _reps(self, stat: str) -> np.ndarray:
+        if stat not in BOOTSTRAP_STATS:
+            raise ValueError(f"stat must be one of {BOOTSTRAP_STATS}, not {stat!r}")
+        return getattr(self, stat + "_reps")
+
+    def se(self, stat: str = "auc") -> np.ndarray:
+        """[K]: the replicates' standard deviation (ddof = 1; 0 with one replicate)"""
+        r = self._reps(stat)
+        return r.std(axis=1, ddof=1) if r.shape[1] > 1 else np.zeros(r.shape[0])
+
+    def ci(self, level: float = 0.95, stat: str = "auc"):
+        """(lo [K], hi [K]): the percentile interval, `np.quantile(reps, (1 -+ level) / 2, method="linear")`"""
+        level = _check_level(level)
+        r = self._reps(stat)
+        return (np.quantile(r, (1.0 - level) / 2.0, axis=1, method="linear"), np.quantile(r, (1.0 + level) / 2.0, axis=1, method="linear"))
+
+    def _diffs(self, stat: str):
+        r = self._reps(stat)
+        return [r[k] - r[l] for k, l in _pairs(r.shape[0])]
+
+    def diff_ci(self, level: float = 0.95, stat: str = "auc"):
+        """(lo [P], hi [P]) over the pairs (k, l), k <= l, row by row (the order of `AucTest`'s upper triangles): the percentile
+        interval of stat[k] - stat[l] over the shared replicates; [0, 0] for k == l"""
+        level = _check_level(level)
+        d = np.stack(self._diffs(stat))
+        return (np.quantile(d, (1.0 - level) / 2.0, axis=1, method="linear"), np.quantile(d, (1.0 + level) / 2.0, axis=1, method="linear"))
+
+    def diff_p(self, stat: str = "auc") -> np.ndarray:
+        """[P], the same pairs: the two-sided bootstrap p-value of "the difference is 0", 2 min(#(d <= 0) + 1, #(d >= 0) + 1) / (B + 1)
+        capped at 1"""
+        B = self.replicates
+        return np.array([min(1.0, 2.0 * min(int((d <= 0).sum()) + 1, int((d >= 0).sum()) + 1) / (B + 1)) for d in self._diffs(stat)])
+
+    def to_json(self, level: float = 0.95) -> dict:
+        """ints, floats and lists: strict JSON"""
+        lst = lambda a: [float(x) for x in a]                                                        # noqa: E731
+        out = {"n_pos": self.n_pos, "n_neg": self.n_neg, "replicates": self.replicates, "seed": self.seed, "tpr": self.tpr,
+               "level": float(_check_level(level)), "pairs": [list(p) for p in _pairs(self.auc.size)]}
+        for stat in BOOTSTRAP_STATS:
+            (lo, hi), (dlo, dhi) = self.ci(level, stat), self.diff_ci(level, stat)
+            out[stat] = {"value": lst(getattr(self, stat)), "se": lst(self.se(stat)), "ci_lo": lst(lo), "ci_hi": lst(hi),
+                         "diff_ci_lo": lst(dlo), "diff_ci_hi": lst(dhi), "diff_p": lst(self.diff_p(stat))}
+        return out
+
+    def __repr__(self):
+        return (f"Bootstrap(auc={self.auc.tolist()}, ap={self.ap.tolist()}, fpr={self.fpr.tolist()}, replicates={self.replicates}, "
+                f"n_pos={self.n_pos}, n_neg={self.n_neg})")
+
+
+def bootstrap(labels, scores, replicates: int = 2000, seed: int = 0, tpr: float = 0.95) -> Optional[Bootstrap]:
+    """Bootstrap intervals and paired tests for the ROC AUC, the average precision and the FPR at the TPR level `tpr` of `scores` [n]
+    or [K, n] -- K <= 8 models scored on the same n samples in the same order -- against `labels` [n] (1: positive, 0: negative,
+    anything else is ignored): see `Bootstrap`.  None when there is no positive or no negative.
+
+    The resampling is stratified and stated exactly (`bootstrap_multiplicities_np`: Philox4x32-10 counters, so a replicate is a
+    function of (seed, b) alone and neither of the order of evaluation nor of the device).  A position is selected by multiply-shift
+    without rejection, (w * size) >> 32: its probability is off from 1 / size by less than size / 2^32 (2.4e-4 relative at the cap of
+    2^20 samples, 2e-6 at 10 000), far below what B <= 65 536 replicates resolve.
+
+    GPU tensors, or a list of K GPU tensors of one length (stacked on the device), go through `eoe_bootstrap_counts` (csrc/bootstrap.hip:
+    every replicate is resampled and counted on the device, 3 K (B + 1) numbers come back in one copy); host arrays and CPU tensors
+    through `bootstrap_np`.  Both give the same integers, the APs agree within 4 n 2^-53, and everything after the tables is the same
+    host code.  Scores are compared as float32 on the device; host float32 stays float32, anything else is compared as float64.
+
+    ValueError for a NaN score among the positives and negatives, for K outside [1, 8], n outside [2, 2^20], `replicates` outside
+    [1, 65 536], `tpr` outside (0, 1] and for another number of labels than scores."""
+    seed, tpr = _check_seed(seed), _check_tpr(tpr)
+    if isinstance(scores, (list, tuple)) and len(scores) > 0 and all(_is_gpu_tensor(x) for x in scores):
+        import torch
+        if len({int(x.numel()) for x in scores}) != 1:
+            raise ValueError(f"the score columns must have one length, not {[int(x.numel()) for x in scores]}")
+        if len(scores) > BOOTSTRAP_MAX_COLUMNS:
+            raise ValueError(f"a bootstrap takes between 1 and {BOOTSTRAP_MAX_COLUMNS} score columns, not {len(scores)}")
+        scores = torch.stack([x.detach().reshape(-1).float() for x in scores])
+    if _is_gpu_tensor(scores):
+        u2, fps, ap, m, n0, bad = bootstrap_device(labels, scores, replicates, seed, tpr)
+        if bad:
+            raise ValueError("scores contain NaN")
+    else:
+        if isinstance(scores, (list, tuple)):
+            if len(scores) == 0:
+                _check_bootstrap_shape(2, 0, 2, 1)
+            if len({int(np.asarray(_to_host(x)).size) for x in scores}) != 1:
+                raise ValueError("the score columns must have one length")
+            scores = np.stack([np.asarray(_to_host(x)).ravel() for x in scores])
+        s = np.asarray(_to_host(scores))
+        if s.ndim > 1 and s.shape[0] == 0:
+            _check_bootstrap_shape(2, 0, 2, 1)
+        u2, fps, ap, m, n0 = bootstrap_np(labels, s, replicates, seed, tpr)
+    if m == 0 or n0 == 0:
+        return None
+    return Bootstrap(u2, fps, ap, m, n0, seed, tpr)

@@ -52,6 +52,10 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
     class's last seed, the paired test of the seeds' AUCs over the shared test split, from exact integer pair counts taken on the
     device (`eoe_delong_counts`, csrc/delong.hip; `metrics.delong`), kept in `trainer.auc_tests` and logged as JSON.  The reference
     has nothing of the kind.  Off by default.
+  * `bootstrap=B` gives the same for the numbers DeLong does not cover: percentile intervals of the AUC, the average precision and the
+    FPR at 95 % TPR from B stratified bootstrap replicates per evaluation and, after a class's last seed, the paired comparison of
+    the seeds, every replicate resampled and counted on the device (`eoe_bootstrap_counts`, csrc/bootstrap.hip; `metrics.bootstrap`),
+    kept in `trainer.bootstraps` and logged as JSON.  The reference has nothing of the kind.  Off by default.
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
@@ -65,7 +69,8 @@ import torch
 
 from .. import ops, parallel
 from ..metrics import (ROC, PRC, roc_auc, average_precision, auc_ap_device, curves_device, mean_plot, roc_curve, precision_recall_curve,
-                       score_extremes, score_histograms, class_breakdown, delong, DELONG_MAX_COLUMNS)
+                       score_extremes, score_histograms, class_breakdown, delong, DELONG_MAX_COLUMNS, bootstrap as bootstrap_stats,
+                       BOOTSTRAP_MAX_COLUMNS, BOOTSTRAP_MAX_REPLICATES)
 from ..msm import apply_msms, check_supported
 from ..normalize import GcnNormalize
 from ..optim import FusedAdam
@@ -159,7 +164,8 @@ class ADTrainer(ABC):
                  previews: bool = False, histograms: bool = False, extremes: int = 0, explain: bool = False,
                  attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None,
                  cam: bool = False, cam_layer: str = "layer4", cam_mode: str = "gradcam", neighbors: int = 0,
-                 knn_baseline: bool = False, mahalanobis_baseline: bool = False, mahalanobis_shrinkage="ledoit_wolf"):
+                 knn_baseline: bool = False, mahalanobis_baseline: bool = False, mahalanobis_shrinkage="ledoit_wolf",
+                 bootstrap: Optional[int] = None, bootstrap_level: float = 0.95, bootstrap_seed: int = 0):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -267,7 +273,18 @@ class ADTrainer(ABC):
         explains.  Seeds whose label vectors differ are not compared (one logged line).  The scores are kept only inside `run`, from
         a class's first seed to its comparison; `eval_cls` called on its own keeps nothing.  A NaN test score costs that evaluation
         its interval (one logged line, no attribute, no file) and its place in the comparison, not the run.  `run` starts with an
-        empty `self.auc_tests`.  Default None: no launch, no file, no attribute, the same text line."""
+        empty `self.auc_tests`.  Default None: no launch, no file, no attribute, the same text line.
+
+        `bootstrap=B` (an integer in [1, 65 536]; anything else raises here), with `bootstrap_level` (a confidence level in (0, 1)) and
+        `bootstrap_seed`: where `eval_cls` computes the AUC it also resamples the test scores B times (`eoe_amd.metrics.bootstrap`: one
+        call for device scores, 9 (B + 1) numbers back) -- the stratified bootstrap of the AUC, the average precision and the FPR at
+        95 % TPR.  The `Bootstrap` is kept in `self.bootstraps[cls][seed]`, the percentile intervals are attached to the returned
+        containers (`roc.boot_ci`, `prc.ci`, `prc.se`), `to_json(bootstrap_level)` is logged as `eval_cls{cls}_it{seed}_bootstrap` and
+        the `Eval:` text line ends with the AP's interval.  In `run`, after a class's last seed, the seeds' scores (the first 8) share
+        one set of replicates, provided their test labels agree: the intervals and p-values of every pair's difference in AUC, AP and
+        FPR are logged as `eval_cls{cls}_bootstrap_compare`.  Independent of `auc_ci`.  A NaN score costs the interval and one logged
+        line, not the run.  `run` starts with an empty `self.bootstraps`.  Default None: no launch, no file, no attribute, the same
+        text line."""
         self.previews = bool(previews)
         self.model = model.cpu() if model is not None else model
         # replay forward + loss + backward + scores of the full-size step batch from a HIP graph (eoe_amd.GraphedStep): for the
@@ -356,6 +373,17 @@ class ADTrainer(ABC):
             raise ValueError(f"auc_ci must be None or a confidence level in (0, 1), not {auc_ci!r}")
         self.auc_ci = None if auc_ci is None else float(auc_ci)
         self.auc_tests = {}                                 # cls -> AucTest over the seeds' scores, filled by run when auc_ci and seeds > 1
+        if bootstrap is not None and (isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer))
+                                      or not 1 <= bootstrap <= BOOTSTRAP_MAX_REPLICATES):
+            raise ValueError(f"bootstrap must be None or a number of replicates in [1, {BOOTSTRAP_MAX_REPLICATES}], not {bootstrap!r}")
+        if isinstance(bootstrap_level, bool) or not isinstance(bootstrap_level, (int, float)) or not 0.0 < bootstrap_level < 1.0:
+            raise ValueError(f"bootstrap_level must be a confidence level in (0, 1), not {bootstrap_level!r}")
+        if isinstance(bootstrap_seed, bool) or not isinstance(bootstrap_seed, (int, np.integer)) or not 0 <= bootstrap_seed < 1 << 64:
+            raise ValueError(f"bootstrap_seed must be an integer in [0, 2^64), not {bootstrap_seed!r}")
+        self.bootstrap = None if bootstrap is None else int(bootstrap)
+        self.bootstrap_level, self.bootstrap_seed = float(bootstrap_level), int(bootstrap_seed)
+        self.bootstraps = {}                                # cls -> {seed: Bootstrap}, filled by eval_cls when bootstrap
+        self._boot_scores = None
         self._seed_scores = None                            # [(seed, labels, scores)] of the class `run` is at, while it has seeds to compare
 
     # ------------------------------------------------------------------------------------------- run
@@ -480,11 +508,14 @@ class ADTrainer(ABC):
         self.breakdowns = {}
         self.auc_tests = {}
         self._seed_scores = None
+        self.bootstraps = {}
+        self._boot_scores = None
         for c, cstr in enumerate(self.classes):
             if c not in wanted:
                 continue
             # auc_ci: the seeds' scores are kept, where they are, only from here to the comparison below
             self._seed_scores = [] if self.auc_ci is not None and test and run_seeds > 1 else None
+            self._boot_scores = [] if self.bootstrap is not None and test and run_seeds > 1 else None
             for seed in range(run_seeds):
                 self.logger.print(f'------ start training cls {c} "{cstr}" ------')
                 preset = None
@@ -508,6 +539,8 @@ class ADTrainer(ABC):
                 models[c].append(model if (model is None or ADTrainer.KEEP_SNAPSHOT_IN_RAM) else None)
             if self._seed_scores is not None:
                 self._compare_seeds(c)
+            if self._boot_scores is not None:
+                self._compare_seeds_bootstrap(c)
             if self.with_curves:
                 # the seeds' "mean" curves of this class, in the reference's order (:308-313; plot_many skips the seeds without a curve)
                 for k, lst in (("mean_train_rocs", train_rocs[c]), ("mean_eval_rocs", eval_rocs[c]), ("mean_eval_prcs", eval_prcs[c])):
@@ -704,6 +737,44 @@ class ADTrainer(ABC):
             return
         self.auc_tests[cls] = test
         self.logger.logjson(f"eval_cls{cls}_auc_compare", {"seeds": [s for s, _, _ in kept], **test.to_json(self.auc_ci)})
+
+    def _log_bootstrap(self, roc: ROC, prc: PRC, la: np.ndarray, la_t: torch.Tensor, sc_t: torch.Tensor, cls: int, seed: int) -> str:
+        """the bootstrap of one evaluation's AUC, AP and FPR at 95 % TPR (`bootstrap=B` only): kept, attached to `roc` and `prc`, logged
+        as JSON, and returned as the tail of the `Eval:` text line.  While `run` has seeds to compare, the scores are kept where they
+        are.  A NaN score costs the intervals, not the run: one logged line, no attribute, no file."""
+        try:
+            boot = bootstrap_stats(la_t, sc_t, self.bootstrap, self.bootstrap_seed)       # both classes are present: the caller has an AUC
+        except ValueError as e:
+            self.logger.logtxt(f"Eval: class {cls}, seed {seed}: no bootstrap intervals ({e}).")
+            return ""
+        level = self.bootstrap_level
+        (alo,), (ahi,) = boot.ci(level, "auc")
+        (lo,), (hi,) = boot.ci(level, "ap")
+        roc.boot_ci = (float(alo), float(ahi))
+        prc.ci, prc.se = (float(lo), float(hi)), float(boot.se("ap")[0])
+        self.bootstraps.setdefault(cls, {})[seed] = boot
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_bootstrap", boot.to_json(level))
+        if self._boot_scores is not None:
+            self._boot_scores.append((seed, la, sc_t.detach().reshape(-1).float()))
+        return f" {level * 100:g}% bootstrap CI of the AP [{lo * 100:04.2f}%, {hi * 100:04.2f}%]."
+
+    def _compare_seeds_bootstrap(self, cls: int):
+        """after a class's last seed (`bootstrap=B` only): the seeds' scores under one set of replicates over the shared test split"""
+        kept, self._boot_scores = self._boot_scores or [], None
+        if len(kept) < 2:
+            return
+        if len(kept) > BOOTSTRAP_MAX_COLUMNS:
+            self.logger.logtxt(f"Eval: class {cls}: comparing the first {BOOTSTRAP_MAX_COLUMNS} of {len(kept)} seeds by bootstrap.")
+            kept = kept[:BOOTSTRAP_MAX_COLUMNS]
+        labels = kept[0][1]
+        if any(not np.array_equal(la, labels) for _, la, _ in kept[1:]):
+            self.logger.logtxt(f"Eval: class {cls}: the seeds' test labels differ; they are not compared by bootstrap.")
+            return
+        scores = [sc for _, _, sc in kept]
+        boot = bootstrap_stats(labels, scores if scores[0].is_cuda else torch.stack(scores).numpy(), self.bootstrap, self.bootstrap_seed)
+        if boot is None:
+            return
+        self.logger.logjson(f"eval_cls{cls}_bootstrap_compare", {"seeds": [s for s, _, _ in kept], **boot.to_json(self.bootstrap_level)})
 
     def breakdown_matrix(self) -> np.ndarray:
         """float64 [no_classes, no_classes]: entry [c, k] is the mean over the seeds of the AUC of task c against class k
@@ -1095,6 +1166,8 @@ class ADTrainer(ABC):
                     cls_roc.fpr, cls_roc.tpr, cls_roc.ths = roc_curve(la, sc)
                     cls_prc.prec, cls_prc.rec, cls_prc.ths = precision_recall_curve(la, sc)
             interval = self._log_auc_ci(cls_roc, la, la_t, sc_t, cls, seed) if self.auc_ci is not None else ""
+            if self.bootstrap is not None:
+                interval += self._log_bootstrap(cls_roc, cls_prc, la, la_t, sc_t, cls, seed)
             self.logger.logtxt(f'Eval: class "{clsstr}" yields {cls_roc.auc * 100:04.2f}% AUC and '
                                f'{cls_prc.avg_prec * 100:04.2f}% average precision (seed {seed}).' + interval)
         else:

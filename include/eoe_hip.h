@@ -948,6 +948,37 @@ int eoe_class_breakdown(const float* scores, const int32_t* class_ids, const uin
 size_t eoe_delong_scratch_bytes(int n, int K);
 int eoe_delong_slices(int n, int K);
 int eoe_delong_counts(const float* scores, const int64_t* labels, int n, int K, int64_t* out, void* scratch, void* stream);
+/* The stratified, paired bootstrap of AUC, AP and FPR at a TPR level, resampled and counted on the device (csrc/bootstrap.hip).
+ * Positives: label 1 (m of them); negatives: label 0 (n0); any other label is in neither.  Each stratum is numbered in ascending sample
+ * index.  Replicate b draws m times with replacement from the positives and n0 times from the negatives, and all K columns share the draws:
+ *   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32)
+ *   and counter (j, b, stratum, 0), stratum 0 for the negatives and 1 for the positives, gives the draws 4j .. 4j+3 of that (replicate,
+ *   stratum); the unused words of the last call are dropped; a word w selects position (w * size) >> 32 of its stratum (multiply-shift
+ *   without rejection: a position's probability is off by less than size / 2^32).
+ * With c[i] the multiplicity of sample i in replicate b, per column k (IEEE fp32 compares: -0.0 == 0.0, the infinities are ordinary values):
+ *   out_u2  int64 [K][B+1] sum over (positive i, negative j) of c[i] c[j] (2 [s_i > s_j] + [s_i == s_j]); the AUC is u2 / (2 m n0)
+ *   out_fps int64 [K][B+1] sum over negatives j of c[j] [s_j >= t], t the score at place p of the resampled positives in descending order
+ *                         with multiplicity, p the smallest integer with p / m >= tpr in float64; the FPR is fps / n0
+ *   out_ap  f64   [K][B+1] sum over the distinct scores in descending order of (tps_g - tps_{g-1}) / m * (tps_g / (tps_g + fps_g)) with the
+ *                         weighted cumulative counts: sklearn's average_precision_score of the resample.  Summed in a fixed order (within
+ *                         about n 2^-53 of any other order).
+ *   Entry [k][b] belongs to replicate b < B; entry [k][B] is the same number on the full sample (every multiplicity 1), so that the
+ *   point estimates need no second pass over the scores.
+ *   counts  int32 [3] = { m, n0, the number of NaN scores among the positives and negatives of all columns }; when the last is not 0 the
+ *                         tables are unspecified (nothing is read or written out of range).  With m == 0 or n0 == 0 the tables are zeros.
+ * u2 and fps are exact integers and all three tables are the same bytes on every run: integer LDS atomics, no floating-point atomics.
+ *   scores fp32 [K][n] (column k at scores + k n), labels int64 [n], the outputs: all DEVICE; 4-byte aligned (labels, tables: 8-byte).
+ *   2 <= n <= 2^20, 1 <= K <= 8, 1 <= B <= 65536, 0 < tpr <= 1.
+ *   scratch: eoe_bootstrap_scratch_bytes(n, K, B) bytes (0 outside the ranges; it does not grow with B), 8-byte aligned, may be dirty.
+ *   Five enqueues on `stream` (a memset and four launches).  A workgroup of the replicate pass counts EOE_BOOTSTRAP_CHUNK sorted
+ *   positions at a time in LDS and regenerates its draws once per chunk.
+ * eoe_bootstrap_draws: the multiplicities of replicate b per sample, out int32 [n] (0 for an ignored label), for tests and diagnosis;
+ *   0 <= b < 65536; scratch: eoe_bootstrap_scratch_bytes(n, 1, 1) bytes; a memset and two launches. */
+#define EOE_BOOTSTRAP_CHUNK 16384
+size_t eoe_bootstrap_scratch_bytes(int n, int K, int B);
+int eoe_bootstrap_counts(const float* scores, const int64_t* labels, int n, int K, int B, uint64_t seed, double tpr, int64_t* out_u2,
+                         int64_t* out_fps, double* out_ap, int32_t* counts, void* scratch, void* stream);
+int eoe_bootstrap_draws(const int64_t* labels, int n, int b, uint64_t seed, int32_t* out, void* scratch, void* stream);
 /* Nearest neighbours in feature space (csrc/knn.hip): for every row of q the k rows of r with the smallest squared Euclidean distance,
  * ascending by distance, equal distances by ascending reference index -- np.argsort(d2_row, kind="stable")[:k] -- each with its distance.
  *   q fp32 [nq, D] with row stride ldq, r fp32 [nr, D] with row stride ldr (ldq, ldr >= D; nothing is read past column D of a row);
