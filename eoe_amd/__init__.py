@@ -28,9 +28,10 @@ from .explain import input_gradient, saliency, overlay, attention_rollout  # noq
 from .metrics import Breakdown, class_breakdown  # noqa: F401
 from .metrics import AucTest, delong     # noqa: F401
 from .metrics import Bootstrap, bootstrap  # noqa: F401
+from . import coreset                    # noqa: F401,E402
 
 __all__ = ["set_compute_dtype", "compute_dtype", "hsc_loss", "hsc_score", "bce_loss", "bce_score", "linear",
            "FusedAdam", "FusedSGD", "GraphedStep", "set_parity_mode", "parity_mode", "set_grad_scale", "grad_scale",
            "default_grad_scale", "fit_statistics", "gcn_normalize", "GlobalContrastNormalization", "GcnNormalize", "OEPool", "run_evolution",
            "image_grid", "explain", "input_gradient", "saliency", "overlay", "attention_rollout",
-           "Breakdown", "class_breakdown", "AucTest", "delong", "Bootstrap", "bootstrap"]
+           "Breakdown", "class_breakdown", "AucTest", "delong", "Bootstrap", "bootstrap", "coreset"]

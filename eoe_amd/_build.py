@@ -23,7 +23,7 @@ SOURCES = ["api.cpp", "gemm.hip", "gemm_tn.hip", "elementwise.hip", "attention.h
            "vit.cpp", "parity.hip", "gemm256.hip", "comm.cpp", "gemm_tn256.hip", "gemm_w8.hip", "probe.hip",
            "msm.hip", "sharpen.hip", "clip_text.hip", "clip_text_driver.cpp", "normstats.hip", "evolve.hip", "curves.hip", "grid.hip",
            "attention_long.hip", "hist.hip", "topk.hip", "explain.hip", "rollout.hip", "breakdown.hip",
-           "delong.hip", "gradcam.hip", "knn.hip", "mahalanobis.hip", "bootstrap.hip"]
+           "delong.hip", "gradcam.hip", "knn.hip", "mahalanobis.hip", "bootstrap.hip", "coreset.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 # gemm_w8.hip names its 128 accumulator registers literally: the compiler must not park spilled VGPRs in AGPRs there (the file's header)
 EXTRA_CFLAGS = {"gemm_w8.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"]}

@@ -248,6 +248,8 @@ SIGNATURES = {
     "eoe_feature_moments": [_vp, C.c_int, C.c_int, C.c_int] + [_vp] * 6,
     "eoe_mahalanobis_score_scratch_bytes": [C.c_int] * 3,
     "eoe_mahalanobis_score": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 4,
+    "eoe_feature_coreset_scratch_bytes": [C.c_int] * 3,
+    "eoe_feature_coreset": [_vp] + [C.c_int] * 5 + [_vp] * 7,
     "eoe_clip_fwd": [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "eoe_clip_bwd": [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "eoe_clip_score": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
@@ -319,7 +321,7 @@ _RESTYPES = {"eoe_last_error": C.c_char_p, "eoe_conv_f32_wgrad_workspace": _sz, 
              "eoe_class_breakdown_scratch_bytes": _sz, "eoe_delong_scratch_bytes": _sz,
              "eoe_bootstrap_scratch_bytes": _sz,
              "eoe_feature_knn_scratch_bytes": _sz, "eoe_feature_moments_scratch_bytes": _sz,
-             "eoe_mahalanobis_score_scratch_bytes": _sz}
+             "eoe_mahalanobis_score_scratch_bytes": _sz, "eoe_feature_coreset_scratch_bytes": _sz}
 
 
 def header_symbols():

@@ -59,6 +59,7 @@ What differs, deliberately (SURVEY.md sections 3.1 and 8):
 Datasets, loggers with tensorboard/PDF output and the CLIP text objective are out of scope.
 """
 import json
+import math
 import os
 from abc import ABC, abstractmethod
 from copy import deepcopy
@@ -165,7 +166,7 @@ class ADTrainer(ABC):
                  attention: bool = False, breakdown: bool = False, breakdown_tpr: float = 0.95, auc_ci: Optional[float] = None,
                  cam: bool = False, cam_layer: str = "layer4", cam_mode: str = "gradcam", neighbors: int = 0,
                  knn_baseline: bool = False, mahalanobis_baseline: bool = False, mahalanobis_shrinkage="ledoit_wolf",
-                 bootstrap: Optional[int] = None, bootstrap_level: float = 0.95, bootstrap_seed: int = 0):
+                 bootstrap: Optional[int] = None, bootstrap_level: float = 0.95, bootstrap_seed: int = 0, knn_coreset=0):
         """same parameters as the reference (`ad_trainer.py:98-164`).  `dataset` is either a step-batch source
         (eoe_amd.data: an object with `.loaders(batch_size)`, `.nominal_label`, `.normalize`) or a callable
         `(cls, seed) -> source`; `classes` names the classes to iterate (default: one class "0").
@@ -239,7 +240,13 @@ class ADTrainer(ABC):
         `normal_pictures` the picture `eval_cls{cls}-{clsstr}_it{seed}_extremes_neighbors`, each row an image and its k neighbours.
         `knn_baseline=True` (needs `neighbors`) scores the whole test split by the mean distance to its k nearest normal features,
         the standard non-parametric baseline: AUC and AP in `self.knn_results[cls]`, `eval_cls{cls}_it{seed}_knn` and a text line.
-        Both default off: no launch, no file, the same lines and return values.)  Default off:
+        `knn_coreset=m` (needs `neighbors`; an int >= 1 or a float in (0, 1), the share of the normal rows; 0: off) replaces the
+        normal features in both searches by their greedy k-center coreset (`eoe_amd.coreset.kcenter`, csrc/coreset.hip; start at
+        normal row 0, m clamped to [neighbors, n_normal]): the memory bank a feature-bank detector ships.  The `Coreset` is kept in
+        `self.coresets[f"eval_cls{cls}_it{seed}"]` (`run` starts with it empty), its `as_dict` with dataset indices goes to
+        `eval_cls{cls}_it{seed}_coreset`, `self.knn_results[cls]` gains "coreset": {m, n, cover}, and with `normal_pictures` the
+        first 32 centres, the most mutually distant normal images, are logged as `eval_cls{cls}-{clsstr}_it{seed}_coreset`.
+        All default off: no launch, no file, the same lines and return values.)  Default off:
         no launch, no file, the same return values and files as before.
 
         `mahalanobis_baseline=True` (independent of `extremes` and `neighbors`; needs a source with `normal_inputs` and a model with a
@@ -358,6 +365,16 @@ class ADTrainer(ABC):
                              "at least 1")
         self.neighbors = {}                                 # f"eval_cls{c}_it{seed}" -> eoe_amd.neighbors.Neighbors, filled by eval_cls when n_neighbors > 0
         self.knn_results = {}                               # cls -> {k, auc, avg_prec, n_normal, D} of the last seed, filled by eval_cls when with_knn_baseline
+        is_share = isinstance(knn_coreset, (float, np.floating))
+        if isinstance(knn_coreset, bool) or not (is_share or isinstance(knn_coreset, (int, np.integer))) \
+                or (is_share and not 0.0 < knn_coreset < 1.0) or (not is_share and knn_coreset < 0):
+            raise ValueError(f"knn_coreset must be a number of centres >= 1, a share of the normal rows in (0, 1) or 0 (off), "
+                             f"not {knn_coreset!r}")
+        self.knn_coreset = float(knn_coreset) if is_share else int(knn_coreset)
+        if self.knn_coreset and self.n_neighbors == 0:
+            raise ValueError("knn_coreset=m searches the neighbors=k nearest rows among m representatives of the normal features: "
+                             "neighbors must be at least 1")
+        self.coresets = {}                                  # f"eval_cls{c}_it{seed}" -> eoe_amd.coreset.Coreset, filled by eval_cls when knn_coreset
         self.with_mahalanobis = bool(mahalanobis_baseline)
         if self.with_mahalanobis:
             from ..mahalanobis import check_shrinkage
@@ -504,6 +521,7 @@ class ADTrainer(ABC):
         self.cams = {}
         self.neighbors = {}
         self.knn_results = {}
+        self.coresets = {}
         self.mahalanobis_results = {}
         self.breakdowns = {}
         self.auc_tests = {}
@@ -929,6 +947,20 @@ class ADTrainer(ABC):
         self.logger.logjson(f"eval_cls{cls}_it{seed}_mahalanobis", res)
         self.logger.logtxt(f'Eval: class "{clsstr}" (seed {seed}) (Mahalanobis baseline: {auc * 100:04.2f}% AUC)')
 
+    def _log_coreset(self, ds, refs, normal_ids, cls: int, clsstr: str, seed: int):
+        """the greedy k-center coreset of the normal features (`knn_coreset=m` only), kept and logged: (the `Coreset`, its centres as
+        rows of `refs`, on the device of `refs`)"""
+        from .. import coreset
+        n = int(refs.shape[0])
+        m = self.knn_coreset if isinstance(self.knn_coreset, int) else int(math.ceil(self.knn_coreset * n))
+        cs = coreset.kcenter(refs, max(1, min(n, max(m, self.n_neighbors))), 0)
+        self.coresets[f"eval_cls{cls}_it{seed}"] = cs
+        self.logger.logjson(f"eval_cls{cls}_it{seed}_coreset", cs.as_dict(ref_ids=normal_ids))
+        centres = cs.idx[cs.idx >= 0]
+        if self.logger.active and hasattr(ds, "normal_pictures"):
+            self.logger.logimg(f"eval_cls{cls}-{clsstr}_it{seed}_coreset", ds.normal_pictures(centres[:32].cpu()).float())
+        return cs, centres
+
     def _log_neighbors(self, model, ds, ex, la_t, test_feats, nominal: int, cls: int, clsstr: str, seed: int, kept: dict):
         """the k nearest normal training images of the extremes picture's rows in feature space (`neighbors=k` only): kept, logged
         as JSON and, under an active logger with `normal_pictures`, as a picture of each row's image followed by its neighbours;
@@ -941,7 +973,13 @@ class ADTrainer(ABC):
         n_normal = ds.n_normal
         refs, normal_ids = self._normal_features(model, ds, nominal, kept)
         queries = knn.embed(model, [ds.test_inputs(rows)[:2]], trainer=self, nominal=nominal)
+        cs = centres = None
+        if self.knn_coreset:
+            cs, centres = self._log_coreset(ds, refs, normal_ids, cls, clsstr, seed)
+            refs = refs[centres]
         neigh = knn.feature_knn(queries, refs, k)
+        if centres is not None:                             # rows of the coreset -> normal rows, as without it
+            neigh.idx = torch.where(neigh.idx >= 0, centres[neigh.idx.clamp(min=0)], neigh.idx)
         self.neighbors[f"eval_cls{cls}_it{seed}"] = neigh
         self.logger.logjson(f"eval_cls{cls}_it{seed}_extremes_neighbors", neigh.as_dict(row_ids=rows, ref_ids=normal_ids))
         if self.logger.active and hasattr(ds, "test_pictures") and hasattr(ds, "normal_pictures"):
@@ -963,6 +1001,8 @@ class ADTrainer(ABC):
         else:
             auc, ap = roc_auc(la.numpy(), score.numpy()), average_precision(la.numpy(), score.numpy())
         res = {"k": k, "auc": float(auc), "avg_prec": float(ap), "n_normal": int(n_normal), "D": int(refs.shape[1])}
+        if cs is not None:
+            res["coreset"] = {"m": int(centres.numel()), "n": cs.n, "cover": cs.cover()}
         self.knn_results[cls] = res
         self.logger.logjson(f"eval_cls{cls}_it{seed}_knn", res)
         self.logger.logtxt(f'Eval: class "{clsstr}" (seed {seed}) (k-NN baseline: {auc * 100:04.2f}% AUC)')

@@ -1031,6 +1031,28 @@ int eoe_feature_moments(const float* x, int ld, int n, int D, float* mean, doubl
 size_t eoe_mahalanobis_score_scratch_bytes(int nq, int D, int P);
 int eoe_mahalanobis_score(const float* x, int ldx, int nq, int D, const float* mean, const float* W, int ldw, int P, int lower, float* d2,
                           int* count, void* scratch, void* stream);
+/* Greedy k-center (farthest-point) coreset of the rows of x (csrc/coreset.hip): idx[0] = start; idx[t], t >= 1, is the eligible, not yet
+ * chosen row with the largest squared distance to its nearest centre among idx[0 .. t-1], equal distances to the LOWEST row;
+ * radius[t] is that squared distance, radius[0] = +inf.  A chosen row is never chosen again (m == n: a permutation of the finite rows).
+ *   x fp32 [n, D] with row stride ldx >= D (nothing is read past column D of a row); idx int32 [m], radius fp32 [m], assign int32 [n],
+ *   d2min fp32 [n], counts int32 [2].  All DEVICE, 4-byte aligned; a 16-byte aligned x with ldx % 4 == 0 and D % 4 == 0 takes 16-byte loads,
+ *   anything else element loads with the same bytes in every output.
+ *   assign[i] = the position t of row i's nearest centre, the earliest chosen one on equal distances (updated only on strictly
+ *   smaller); d2min[i] = that squared distance; a centre has its own position and 0.
+ *   A row that holds a NaN or an infinity is never a centre: assign = -1, d2min = NaN.  counts[0] = the number of such rows; counts[1] = 1
+ *   if `start` is one of them, and then every other output is unspecified.  Fewer than m eligible rows: the tail holds idx = -1,
+ *   radius = NaN.
+ *   Distance: sum_d (x_d - c_d)^2 in the difference form in fp32 -- each lane an fmaf chain over its columns in ascending order, then
+ *   the wave's butterfly sum: a fixed order, at most D + 2 roundings on any term, so relative error at most g = (D + 2) 2^-24 /
+ *   (1 - (D + 2) 2^-24); exact on integer-valued features while the sums stay below 2^24.
+ *   m launches chained on `stream`, one streaming pass over x per centre; the next centre's index stays on the device (an integer
+ *   atomicMax of (ordered distance bits, 0xFFFFFFFF - row) per workgroup), the host neither waits nor reads inside the call.  No
+ *   float atomics: two runs give the same bytes.
+ *   1 <= D <= 2048, 1 <= n < 2^24, 1 <= m <= n, 0 <= start < n; EOE_ERR_ARG, naming the argument, before any launch otherwise.
+ *   scratch: eoe_feature_coreset_scratch_bytes(n, D, m) bytes (0 outside the ranges), 16-byte aligned, may be dirty. */
+size_t eoe_feature_coreset_scratch_bytes(int n, int D, int m);
+int eoe_feature_coreset(const float* x, int ldx, int n, int D, int m, int start, int* idx, float* radius, int* assign, float* d2min,
+                        int* counts, void* scratch, void* stream);
 
 /* CLIP text-prompt objective (training/clip.py:66-103): f fp32 [n, d] image features, text fp32 [T, d]
  * (2 <= T <= 64; the frozen, l2-normalised text features prepare_metric returns, clip.py:50-64), l = 100 * f/|f| . text^T;
