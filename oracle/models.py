@@ -332,7 +332,9 @@ class _ChannelGate(nn.Module):
         return self.mlp[1](torch.relu(self.mlp[0](v)))
 
     def forward(self, x):
-        att = self._mlp(x.mean(dim=(2, 3))) + self._mlp(x.amax(dim=(2, 3)))
+        # the reference's own F.max_pool2d over the whole map: among equal maxima the first takes the gradient (amax would split it)
+        mx = F.max_pool2d(x, (x.shape[2], x.shape[3])).flatten(1)
+        att = self._mlp(x.mean(dim=(2, 3))) + self._mlp(mx)
         return x * torch.sigmoid(att)[:, :, None, None]
 
 
@@ -343,7 +345,8 @@ class _SpatialGate(nn.Module):
         self.spatial = _BasicConv()
 
     def forward(self, x):
-        comp = torch.cat([x.amax(dim=1, keepdim=True), x.mean(dim=1, keepdim=True)], dim=1)
+        # torch.max(x, 1)[0] as the reference: one channel takes the gradient, the first among equal maxima (amax would split it)
+        comp = torch.cat([x.max(dim=1, keepdim=True)[0], x.mean(dim=1, keepdim=True)], dim=1)
         return x * torch.sigmoid(self.spatial(comp))
 
 
